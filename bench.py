@@ -2,6 +2,16 @@
 """Headline benchmark of the MI355X ring-arithmetic engine.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload ckks|ntt|ntt15|intt|intt15|bgv|rotate|...] [--batch B]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the outputs of the last step when --dump-outputs is given, and prints the
+line: value / ms_per_step, the roofline of the dominant kernel from the timed region's own events, pipeline_roofline, chip,
+placement.  Everything else listed below (the output check against the CPU checker, the CPU baselines, the per-kernel `step` pass,
+the extra sections of the default line, the one-rank RCCL communicator) runs only with --full.
+
+`--dump-outputs DIR` writes what the timed path computed in its last step (the arrays a caller of that path holds) as
+DIR/<name>.npy in float64, at most 48 MiB in all (a fixed, seeded sample of a larger output), and DIR/manifest.json
+(benchkit/dump.py).  With the same arguments the inputs are the same from run to run.
 
 `--gpus N` with N > 1 and no WORLD_SIZE in the environment launches its own N ranks
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same flags>`),
@@ -49,7 +59,7 @@ to `#section <name> <json>` lines before it and to bench_sections.json (benchkit
                         ms, its share of A_step and the HBM fraction that makes; `step_traffic`: the measured HBM bytes of one
                         step (sum of 2 x FETCH_SIZE + WRITE_SIZE over every kernel, committed rocprofv3 passes of this command)
                         beside A_step / A_min -- a pipeline_roofline above 1 is cross-stage fusion, not a measurement error
-  --roofline-only       drops everything after the timed region (for clean rocprofv3 summaries of the default command)
+  --roofline-only       with --full: drops everything after the timed region again (a plain run is that already)
 
 The workloads, inputs, fences and sections live in benchkit/ (no checker there).  The oracle / compiled reference is used
 only here, only after the timed region, as the checker and as the CPU baseline.
@@ -80,7 +90,7 @@ from benchkit.workloads import NAMES as WORKLOADS       # noqa: E402
 def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="ckks", choices=WORKLOADS)
     ap.add_argument("--batch", type=int, default=0, help="units per GPU per step (0 = BASELINE config value)")
@@ -119,10 +129,21 @@ def parse(argv=None):
                          "cgroup CPU quota of this process allow (at most 64), 0 = skip")
     ap.add_argument("--cpu-node-seconds", type=float, default=5.0, help="CPU budget per process of cpu_baseline_node")
     ap.add_argument("--cpu-section-seconds", type=float, default=1.5, help="CPU budget of the samples inside the c2 / bgv sections")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: output check against the CPU checker, CPU baselines, the per-kernel step "
+                         "pass, the extra sections of the default line, the RCCL communicator of a one-rank run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last step to DIR/<name>.npy (float64, seeded sample "
+                         "when larger than 48 MiB in all) and DIR/manifest.json")
     ap.add_argument("--launcher-selftest", action="store_true",
                     help="exercise only the launcher / rendezvous / timing fences with the gloo backend and a dummy step "
                          "(no engine, no GPU); the line says so and carries no throughput claim")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    return args
 
 
 # =====================================================================================================================
@@ -366,7 +387,7 @@ def main() -> int:
     else:
         t_init = time.perf_counter()
         try:   # "nccl" is RCCL on ROCm; rendezvous + timing fences only
-            hd.init("nccl", device=torch.device(f"cuda:{local}"), force=(world == 1 and not args.no_force_dist))
+            hd.init("nccl", device=torch.device(f"cuda:{local}"), force=(world == 1 and args.full and not args.no_force_dist))
             if dist.is_initialized():
                 hd.barrier()               # the first collective creates the communicator
                 rccl_info = {"initialised": True, "backend": dist.get_backend(), "init_s": round(time.perf_counter() - t_init, 3),
@@ -390,7 +411,7 @@ def main() -> int:
 
     chip = ChipSampler(torch, local)
     run.chip = chip
-    extras = not args.roofline_only
+    extras = args.full and not args.roofline_only
     env_level = os.environ.get("HP_PARITY_LEVEL", "")   # (parsed as hp_ctx_create does: an empty value is level B)
     level = args.parity_level or ("A" if env_level and env_level[0] in "Aa1" else "B")
     run.eng.set_parity_level(level)
@@ -418,6 +439,10 @@ def main() -> int:
         "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": wl.scaling,
         "vs_baseline": None, "dtype": "u64", "data": "synthetic", "config": wl.cfg, "parity_level": level,
     }
+    if args.dump_outputs:
+        from benchkit.dump import dump_outputs
+
+        res["dumped_outputs"] = {"dir": os.path.abspath(args.dump_outputs), "files": dump_outputs(run, wl, os.path.abspath(args.dump_outputs))}
     if share_gpu:
         res["data"] = "synthetic (TEST MODE: the ranks share ONE GPU over gloo; exercises the multi-rank path, not a scaling number)"
         res["backend"] = "gloo"

@@ -29,6 +29,10 @@ class Workload:
         """-> (ok, outputs compared, checker evaluations)"""
         raise NotImplementedError
 
+    def outputs(self):
+        """{name: device tensor}: what a caller of the timed path holds after the last step (bench.py --dump-outputs)"""
+        raise NotImplementedError
+
 
 class Transform(Workload):
     """BASELINE config 2 (ntt / intt: N = 16384, four 50-bit primes, 1024 polynomials) or the transform shape inside the C3
@@ -59,6 +63,9 @@ class Transform(Workload):
 
     def step(self):
         (self.run.eng.intt_ if self.inverse else self.run.eng.ntt_)(self.moduli, self.x)
+
+    def outputs(self):
+        return {"polys": self.x}     # transformed in place, warmup + steps times
 
     def verify(self, lib):
         # the timed buffer has been transformed in place steps+warmup times; check one fresh application of the same call
@@ -98,6 +105,9 @@ class Coeffwise(Workload):
     def step(self):
         f = self.run.eng.poly_mul if self.op == "mul" else self.run.eng.poly_add
         f(self.moduli, self.ab.full, self.bb.full, out=self.out)
+
+    def outputs(self):
+        return {"out": self.out}
 
     def verify(self, lib):
         import numpy as np
@@ -142,6 +152,9 @@ class HksMult(Workload):
     def step(self):
         self.run.eng.ckks_mult_hks(self.mext, self.k, self.alpha, self.ct1, self.ct2, self.key, out=self.out)
 
+    def outputs(self):
+        return {"ct_out": self.out}
+
 
 class EncDec(Workload):
     """either side of the path: encrypt_core on caller-supplied samples, then decrypt_core"""
@@ -167,7 +180,10 @@ class EncDec(Workload):
 
     def step(self):
         eng = self.run.eng
-        eng.rlwe_decrypt_core(self.moduli, eng.rlwe_encrypt_core(self.moduli, self.noise, self.c1, self.pt, self.sk), self.sk)
+        self.result = eng.rlwe_decrypt_core(self.moduli, eng.rlwe_encrypt_core(self.moduli, self.noise, self.c1, self.pt, self.sk), self.sk)
+
+    def outputs(self):
+        return {"decrypted": self.result}
 
 
 class Scheme(Workload):
@@ -244,6 +260,9 @@ class Scheme(Workload):
             eng.ckks_mult(self.mext, ct1, ct2, self.key, out=self.out)
         else:
             eng.bgv_mult(self.mext, self.t, ct1, ct2, self.key, out=self.out)
+
+    def outputs(self):
+        return {"ct_out": self.result}
 
     def _check(self, lib, c1, c2, k):
         if self.name == "rotate":

@@ -45,7 +45,7 @@ def run_bench(flags, timeout=900, env=None, cwd=None):
 @pytest.mark.gpu
 @pytest.mark.parametrize("workload", ["ckks", "ntt"])
 def test_bench_line_has_the_contract_fields(workload):
-    r, full, _ = run_bench(["--workload", workload, "--batch", "8", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1", "--cpu-procs", "0"])
+    r, full, _ = run_bench(["--full", "--workload", workload, "--batch", "8", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1", "--cpu-procs", "0"])
     assert REQUIRED <= set(r), REQUIRED - set(r)
     assert r["n_gpus"] == 1 and r["steps"] == 2 and r["warmup"] == 1 and r["higher_is_better"] is True
     assert r["dtype"] == "u64" and r["data"] == "synthetic" and r["vs_baseline"] is None and r["scaling"] == "weak"
@@ -73,7 +73,7 @@ def test_default_line_carries_both_halves_of_the_metric(tmp_path):
     """The default command (C3, batch 256) with a short CPU budget.  The compact line: hom-mult/s with roofline + verification + CPU
     baselines + one number per section; the sections (side file == `#section` lines): the limb-transform rates at N = 4096..32768, the
     coefficient-wise rates, BASELINE configs 2 and 5 at their exact shapes, level A, hehub's object API -- every one verified."""
-    r, full, _ = run_bench(["--steps", "3", "--warmup", "1", "--cpu-seconds", "1", "--cpu-procs", "2", "--cpu-node-seconds", "1"],
+    r, full, _ = run_bench(["--full", "--steps", "3", "--warmup", "1", "--cpu-seconds", "1", "--cpu-procs", "2", "--cpu-node-seconds", "1"],
                            timeout=1800, cwd=str(tmp_path))
     assert REQUIRED <= set(r) and r["metric"] == "ckks_hom_mult_per_s" and r["config"]["batch_per_gpu"] == 256
     assert r["verified"] is True and r["verify"]["outputs_compared_per_gpu"] == 256 and r["verify"]["checker"] in ("reference", "port")
@@ -156,7 +156,7 @@ def test_default_line_carries_both_halves_of_the_metric(tmp_path):
 
 @pytest.mark.gpu
 def test_roofline_only_line_has_no_side_legs():
-    r, full, _ = run_bench(["--batch", "8", "--steps", "2", "--warmup", "1", "--roofline-only"])
+    r, full, _ = run_bench(["--full", "--batch", "8", "--steps", "2", "--warmup", "1", "--roofline-only"])
     assert "roofline" in r and not ({"ntt", "coeffwise", "cpu_baseline", "cpu_baseline_node", "verified"} & set(full))
 
 
@@ -179,7 +179,7 @@ def test_two_ranks_end_to_end_on_one_gpu():
     from rank 0), with the test switch that lets the two ranks share this box's GPU over gloo."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HP_BENCH_SHARE_GPU"] = "1"
-    _, r, _ = run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1"], timeout=1800, env=env)
+    _, r, _ = run_bench(["--full", "--gpus", "2", "--steps", "2", "--warmup", "1"], timeout=1800, env=env)
     assert r["n_gpus"] == 2 and r["dist_ranks"] == 2 and r["rccl_ranks"] == 0 and r["backend"] == "gloo" and "TEST MODE" in r["data"]
     assert r["verified"] is True and r["verify"]["outputs_compared_per_gpu"] == 256
     assert r["ntt"]["verified"] is True and r["coeffwise"]["mul"]["verified"] is True
@@ -196,10 +196,47 @@ def test_eight_ranks_end_to_end_on_one_gpu(workload, batch):
     line from rank 0 -- in the test mode where the ranks share this box's GPU over gloo."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HP_BENCH_SHARE_GPU"] = "1"
-    r, _, _ = run_bench(["--gpus", "8", "--workload", workload, "--steps", "2", "--warmup", "1", "--no-rates"], timeout=1800, env=env)
+    r, _, _ = run_bench(["--full", "--gpus", "8", "--workload", workload, "--steps", "2", "--warmup", "1", "--no-rates"], timeout=1800, env=env)
     assert r["n_gpus"] == 8 and r["dist_ranks"] == 8 and r["rccl_ranks"] == 0 and r["backend"] == "gloo" and "TEST MODE" in r["data"]
     assert r["scaling"] == "weak" and r["config"]["batch_per_gpu"] == batch
     assert r["verified"] is True and r["verify"]["outputs_compared_per_gpu"] == batch
     assert r["metric"] == ("ckks_hom_mult_per_s" if workload == "ckks" else "bgv_hom_mult_per_s")
     assert abs(r["value"] - 8 * batch * 1e3 / r["ms_per_step"]) < 1e-5 * r["value"]     # whole-job aggregate over the 8 ranks
     assert "cpu_baseline" not in r and "roofline" in r and "pipeline_roofline" in r
+
+
+PLAIN = {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus", "config", "roofline"}
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path, orc):
+    """`bench.py` without --full: the timed steps and the line only (no checker, no CPU legs, no communicator of its own); with
+    --dump-outputs the buffer the last timed step wrote, every word of it the checker's, and the same words from a second run"""
+    import numpy as np
+    import torch
+
+    import params as P
+    from benchkit.inputs import Batch, rand_words
+
+    flags = ["--batch", "8", "--steps", "3", "--warmup", "1", "--dump-outputs"]
+    r, full, _ = run_bench(flags + [str(tmp_path / "a")], cwd=str(tmp_path))
+    assert PLAIN <= set(r) and r["steps"] == 3 and r["warmup"] == 1 and r["metric"] == "ckks_hom_mult_per_s" and r["dtype"] == "u64"
+    assert abs(r["value"] - 8 * 1e3 / r["ms_per_step"]) < 1e-5 * r["value"]
+    assert not ({"verified", "cpu_baseline", "cpu_baseline_node", "step", "ntt", "c2", "bgv", "object_api"} & set(full))
+    assert r["rccl_ranks"] == 0 and r["dist_ranks"] == 1
+    assert full["dumped_outputs"]["files"] == ["ct_out.npy"]
+    got = np.load(tmp_path / "a" / "ct_out.npy")
+    mext = P.C3_MODULI_EXT
+    L, n = len(mext) - 1, 1 << P.C3_LOGN
+    assert got.dtype == np.float64 and got.shape == (8, 2, L - 1, n)
+    # the inputs bench.py made (benchkit.workloads.Scheme: seeds 3 / 1003 / 7, period 3), rebuilt here on the same device
+    b1 = Batch(torch, 8, (2, L, n), mext[:L], "cuda:0", 3, 3)
+    b2 = Batch(torch, 8, (2, L, n), mext[:L], "cuda:0", 1003, 3)
+    key = rand_words(torch, (L, 2, L + 1, n), mext, "cuda:0", 7).cpu().numpy().view(np.uint64)
+    _, h1 = b1.classes()
+    _, h2 = b2.classes()
+    for c in range(3):
+        exp = orc.ckks_mult(mext, h1[c], h2[c], key).astype(np.float64)
+        assert all((got[i] == exp).all() for i in range(c, 8, 3)), c
+    run_bench(flags + [str(tmp_path / "b")], cwd=str(tmp_path))
+    assert (np.load(tmp_path / "b" / "ct_out.npy") == got).all()

@@ -76,7 +76,7 @@ def test_rccl_one_rank_runs_the_multi_gpu_calls():
 @pytest.mark.gpu
 def test_bench_line_reports_an_initialised_rccl_communicator():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "ntt", "--logn", "12", "--batch", "64", "--steps", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", "ntt", "--logn", "12", "--batch", "64", "--steps", "2",
                           "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, (out.stdout[-2000:], out.stderr[-3000:])
@@ -96,7 +96,7 @@ def test_limb_sharded_mode_through_rccl_one_rank(transport):
     output verified against the checker"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HP_SHARDED_FORCE_COLLECTIVES"] = "1"
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "ckks-limb", "--limb-transport", transport, "--steps", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--workload", "ckks-limb", "--limb-transport", transport, "--steps", "2",
                           "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, (out.stdout[-2000:], out.stderr[-3000:])

@@ -2,8 +2,9 @@
 word-for-word (raw lazy u64 words, "Level B" of SURVEY.md section 8) with the
 unmodified reference compiled into oracle/_ref/libhehub_ref.so.
 
-Runs only where the reference was built (this container); skipped on the GPU
-box, where the committed golden vectors (test_oracle_golden.py) take over.
+Where the reference is not built, the `ref` fixture (tests/conftest.py) answers
+with the oracle's results checked against the digests the reference gave for the
+same calls (tests/golden/ref_digests.json, tests/golden/make_ref_digests.py).
 """
 import numpy as np
 import pytest

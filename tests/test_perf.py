@@ -29,7 +29,7 @@ def default_line(tmp_path_factory):
     need_gpu()
     from test_bench_contract import run_bench
 
-    line, full, _ = run_bench(["--steps", "10", "--warmup", "3", "--cpu-seconds", "2", "--cpu-procs", "2", "--cpu-node-seconds", "2"], timeout=1800,
+    line, full, _ = run_bench(["--full", "--steps", "10", "--warmup", "3", "--cpu-seconds", "2", "--cpu-procs", "2", "--cpu-node-seconds", "2"], timeout=1800,
                               cwd=str(tmp_path_factory.mktemp("bench")))
     return line, full
 

@@ -57,7 +57,7 @@ for WL in ckks bgv; do
   F=$OUT/scale.json; [ $WL = bgv ] && F=$OUT/bgv_scale.json
   : > $OUT/lines_$WL.txt
   for n in $SIZES; do
-    python bench.py --gpus $n --workload $WL --no-cpu-baseline --no-rates --no-object-api --steps 20 --warmup 3 2> $OUT/bench_${WL}_$n.err | tail -1 >> $OUT/lines_$WL.txt
+    python bench.py --full --gpus $n --workload $WL --no-cpu-baseline --no-rates --no-object-api --steps 20 --warmup 3 2> $OUT/bench_${WL}_$n.err | tail -1 >> $OUT/lines_$WL.txt
   done
   python - $OUT/lines_$WL.txt > $F <<PY
 import json, sys
@@ -72,7 +72,7 @@ done
 # 4 ---- limb-sharded latency mode, both transports --------------------------------------------------------------------------------
 for TR in p2p allgather; do
   n=$(echo $SIZES | awk '{print $NF}')
-  python bench.py --gpus $n --workload ckks-limb --limb-transport $TR --no-cpu-baseline --steps 20 --warmup 3 2> $OUT/bench_limb_$TR.err | tail -1 > $OUT/limb_$TR.json
+  python bench.py --full --gpus $n --workload ckks-limb --limb-transport $TR --no-cpu-baseline --steps 20 --warmup 3 2> $OUT/bench_limb_$TR.err | tail -1 > $OUT/limb_$TR.json
   python -c "import json; r=json.load(open('$OUT/limb_$TR.json')); print('ckks-limb', '$TR', r['n_gpus'], 'ranks', round(r['value']), r['unit'], r['ms_per_step'], 'ms per step', r.get('verified'))"
 done
 

@@ -17,7 +17,7 @@ kt() {   # kt <name> <bench args...>
   rm -rf $R/gpurun_out/${TAG}_kt_$name $R/gpurun_out/${TAG}_kt_$name.log
 }
 kt default --roofline-only
-kt default_full --cpu-seconds 1 --cpu-procs 0
+kt default_full --full --cpu-seconds 1 --cpu-procs 0
 kt level_a --roofline-only --parity-level A          # the C3 step at the opt-in parity level A (FP64 residue transforms)
 for wl in ntt intt ntt15 intt15 bgv rotate mul add encdec; do kt $wl --workload $wl --steps 3 --warmup 1 --roofline-only; done
 cd $R
