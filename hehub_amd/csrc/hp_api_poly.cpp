@@ -140,7 +140,7 @@ int hp_dev_intt(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, size
 // The transforms as RESIDUES (parity level A as an explicit entry point, whatever the context's level): canonical words through the
 // FP64 kernels of hp_ntt_a.hip.  Forward: every output word == ntt.cpp:145-176's word modulo q, in [0, q).  Inverse: the words of
 // intt_negacyclic_inplace (ntt.h:88-92 = lazy inverse + reduce_strict).  Input words are lazy words of their limb (below 2 q; checked on the
-// device, HP_ERANGE from the next synchronising call); N = 2^11 .. 2^15; every q < 2^50.
+// device, HP_ERANGE from the next synchronising call); N = 2^11 .. 2^15; every q < 2^50 that keeps hehub's fold exact (hp::level_a_modulus).
 static int dev_ntt_residues(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, size_t batch, uint64_t *d_x, int inverse) {
     HP_ENTER(ctx);
     HP_REQUIRE(ctx, moduli, d_x);
@@ -153,7 +153,9 @@ static int dev_ntt_residues(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *
     bool ok = false;
     if ((rc = ensure_plan_a(ctx, plan, &ok))) return rc;
     if (!ok || ctx->force_generic)
-        return fail(ctx, HP_EUNSUPPORTED, "residue transforms need a ring degree of 2^11 .. 2^15 and every modulus below 2^50 (and the tiled kernels enabled)");
+        return fail(ctx, HP_EUNSUPPORTED, "residue transforms need a ring degree of 2^11 .. 2^15 and every modulus below 2^50 with an exact hehub fold (not a prime a "
+                              "little above 2^k or well inside its octave: hehub's lazy words are then not residues below 2q) and the tiled "
+                              "kernels enabled");
     HpNttJob j = batch_job(plan, logn, L, batch, d_x, d_x, L, L, inverse, inverse);
     j.limbs_a = plan->d_limbs_a;
     mark_level_a(ctx);   // (the range guard of the level-A kernels: hp_ctx.cpp range_check)

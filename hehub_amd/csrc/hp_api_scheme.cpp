@@ -33,10 +33,10 @@ namespace {
 
 // Which output moduli k in [k0, k1) may keep their digit rows D[.][k] = NTT_{q_k}(c[j]) in the 48-bit packed format: the rows are
 // workspace (written by the digit-spread launch, read by the inner product, never seen by a caller), so the format is free as
-// long as every word survives it.  A word is the folded output of the lazy transform (ntt.cpp:171-175): with kb = round(log2 q),
-// m = x >> kb and delta = |q - 2^kb| it is x - (m - fix) q, below 2^(kb+1) and not wrapped whenever m * delta < 2^kb.  The
-// transform's input is a strict coefficient row (< max_j q_j) and grows by at most 2q per stage, which bounds m.  Only the tiled
-// kernels and the multi-ciphertext inner-product kernels know the format.
+// long as every word survives it.  A word is the folded output of the lazy transform of a strict coefficient row (< max_j q_j):
+// hp::lazy_fold_bound bounds it.  m_max delta < 2^kb: the fold does not wrap (hehub's word would then be ~2^64) and the word is
+// below 2^(kb+1) for fix = 0, below q + 2^kb for fix = 1 -- below 2^48 for kb <= 46.  Only the tiled kernels and the
+// multi-ciphertext inner-product kernels know the format.
 static u32 spread_pack_mask(const hp_ctx *ctx, const Plan *plan, size_t logn, size_t L, size_t P, size_t k0, size_t k1) {
     // measured (tools/ab/ab_pack.sh): -13..-16 % on the inner product at every tiled ring degree, -1.5 % on the spread launch at
     // N = 32768.  (While the inner product computed 64-bit row addresses per load the extra loads of the two planes ate the
@@ -47,12 +47,8 @@ static u32 spread_pack_mask(const hp_ctx *ctx, const Plan *plan, size_t logn, si
     u32 mask = 0;
     for (size_t k = k0; k < k1; k++) {
         const hp::ModConsts &c = plan->consts[k];
-        const u32 kb = c.k;
-        if (kb < 20 || kb > 46) continue;
-        const u64 pow = (u64)1 << kb, delta = c.q >= pow ? c.q - pow : pow - c.q;
-        const unsigned __int128 xmax = (unsigned __int128)cmax + (unsigned __int128)(2 * logn + 2) * (2 * c.q);
-        const unsigned __int128 m = (xmax >> kb) + 2;
-        if (m * delta < pow) mask |= 1u << k;
+        if (c.k < 20 || c.k > 46) continue;
+        if (hp::lazy_fold_bound(c, cmax, logn).m_delta < ((hp::u128)1 << c.k)) mask |= 1u << k;
     }
     return mask;
 }

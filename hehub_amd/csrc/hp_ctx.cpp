@@ -2,6 +2,7 @@
 // caches of twiddle tables / per-limb constants / gather maps / CRT constants (include/hehub_amd.h, "engine").
 #include "hp_ctx.h"
 
+#include <algorithm>
 #include <cstdlib>
 #include <cstring>
 
@@ -113,16 +114,23 @@ int get_plan(hp_ctx *ctx, size_t logn, const uint64_t *moduli, size_t count, boo
     return contained(ctx, [&] { return get_plan_impl(ctx, logn, moduli, count, with_ntt, out); });
 }
 
-// Parity level A: per-limb records + tables of doubles for a plan whose moduli are all below 2^50 and whose ring degree has
-// tiled kernels.  Built from the same host tables as level B (pairs_to_f64), cached per (q, logn).
+// Parity level A: per-limb records + tables of doubles for a plan whose moduli are all below 2^50, whose ring degree has tiled
+// kernels, and whose every modulus keeps hehub's lazy fold exact, lazy in -> lazy out (hp::level_a_modulus: not so for a
+// prime a little above 2^kb, whose fold wraps for large lazy words, nor for one well inside its octave, whose words reach 2q and
+// more).  Built from the same host tables as level B (pairs_to_f64), cached per (q, logn).
 static int ensure_plan_a_impl(hp_ctx *ctx, const Plan *plan, bool *ok) {
     *ok = false;
     if (plan->a_state == 1) { *ok = true; return HP_OK; }
     if (plan->a_state < 0) return HP_OK;
     const size_t logn = plan->logn;
     bool can = logn >= 11 && logn <= 15;   // (the debug switches that bypass the tiled kernels are looked at per call: LevelScope)
-    for (const hp::ModConsts &c : plan->consts)
+    u64 cmax = 0;
+    for (const hp::ModConsts &c : plan->consts) {
         if (c.q >= ((u64)1 << 50) || c.q < 3) can = false;
+        cmax = std::max(cmax, c.q);
+    }
+    for (const hp::ModConsts &c : plan->consts)
+        if (can && !hp::level_a_modulus(c, cmax, logn)) can = false;
     if (!can) { plan->a_state = -1; return HP_OK; }
     if (!ctx->sh->range_flag) {
         HIP_TRY(ctx, hipMalloc((void **)&ctx->sh->range_flag, sizeof(u32)));

@@ -32,7 +32,8 @@ struct Plan {
     HpLimb *d_limbs = nullptr;
     std::vector<hp::ModConsts> consts;
     // parity level A: the FP64 per-limb records, built on first use (ensure_plan_a); a_state 0 = not tried, 1 = ready,
-    // -1 = not available for this chain (a modulus >= 2^50, or a ring degree without tiled kernels)
+    // -1 = not available for this chain (a modulus >= 2^50 or one hehub's fold is not exact on, hp::level_a_modulus;
+    // or a ring degree without tiled kernels)
     mutable HpLimbA *d_limbs_a = nullptr;
     mutable int a_state = 0;
     size_t logn = 0;

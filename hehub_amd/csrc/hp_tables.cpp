@@ -2,6 +2,7 @@
 #include "hp_tables.h"
 #include <cstring>
 
+#include <algorithm>
 #include <cmath>
 
 namespace hp {
@@ -62,6 +63,23 @@ ModConsts make_consts(u64 q) {
     c.k = (uint32_t)log_modulus(q);
     c.fix = (c.k < 64 && q >= ((u64)1 << c.k)) ? 1u : 0u;
     return c;
+}
+
+FoldBound lazy_fold_bound(const ModConsts &c, u128 x_in, size_t logn) {
+    FoldBound f;
+    const u128 x_end = x_in + (u128)2 * c.q * logn;   // every word entering the fold is below this
+    const u128 pow = (u128)1 << c.k, delta = c.q >= pow ? c.q - pow : pow - c.q;
+    const u128 m_max = (x_end - 1) >> c.k;
+    f.m_delta = m_max * delta;
+    f.wraps = x_end > ((u128)1 << 64) || (c.fix && f.m_delta >= pow);
+    f.word_end = c.fix ? pow + c.q : pow + f.m_delta;
+    return f;
+}
+
+bool level_a_modulus(const ModConsts &c, u64 cmax, size_t logn) {
+    const u128 two_q = (u128)2 * c.q;
+    if (lazy_fold_bound(c, std::max<u128>(two_q, cmax), logn).wraps) return false;   // every word congruent to hehub's
+    return lazy_fold_bound(c, two_q, logn).word_end <= two_q;                        // hehub's words of a caller's lazy row: lazy
 }
 
 std::string check_ntt_modulus(u64 q, size_t logn) {

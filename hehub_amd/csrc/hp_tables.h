@@ -35,6 +35,24 @@ int log_modulus(u64 q);                             // (u64)(log2(q) + 0.5)
 
 ModConsts make_consts(u64 q);
 
+// The fold that ends hehub's lazy transforms (ntt.cpp:171-175 forward, :215-219 inverse): x -= ((x >> kb) - fix) q with
+// kb = round(log2 q), fix = (q >= 2^kb).  Each of the logn butterfly stages raises the largest word by less than 2q (a stage writes
+// x_l + t and x_l + 2q - t with t = mul_mod_harvey_lazy(..) in [0, 2q) whatever the u64 operand), so for input words below x_in
+// the fold sees x < x_in + 2q logn, m = x >> kb <= m_max.  With delta = |q - 2^kb| the folded word is (x mod 2^kb) + m delta for
+// fix = 0 -- never below zero -- and (x mod 2^kb) + q - m delta for fix = 1, which goes below zero (hehub's word is then the
+// wrapped u64, not congruent to x modulo q) once m delta exceeds q: no wrap is guaranteed where m_max delta < 2^kb.
+struct FoldBound {
+    bool wraps;      // some input below x_in may give a word that is not x modulo q (a wrapped fold, or a stage sum past 2^64)
+    u128 m_delta;    // m_max delta: below 2^kb, the fold neither wraps (fix = 1) nor leaves a word at or above 2^(kb+1) (fix = 0)
+    u128 word_end;   // where it does not wrap: every folded word is below this (the forward transform's output word)
+};
+FoldBound lazy_fold_bound(const ModConsts &c, u128 x_in, size_t logn);
+// Parity level A serves q (hp_ctx.cpp ensure_plan_a): its FP64 kernels compute true residues, so hehub's fold must not wrap for any
+// input a pipeline of the chain hands the transform -- a caller's lazy word (< 2q) or a strict row of another modulus (< cmax, the
+// key switch's digit rows: their words may exceed 2q, they stay inside the pipeline).  And level A takes lazy words only (< 2q, the
+// range guard), so hehub's forward words of a caller's lazy row -- words hehub hands back to the caller -- must stay below 2q.
+bool level_a_modulus(const ModConsts &c, u64 cmax, size_t logn);
+
 // Returns "" on success, otherwise the message hehub throws for the same input
 // ("2N doesn't divide (modulus - 1)" / "NTT not supporting primes with bit size > 59 currently.").
 std::string check_ntt_modulus(u64 q, size_t logn);

@@ -69,7 +69,8 @@ void hp_ctx_destroy(hp_ctx *ctx);
  *     to hehub's word modulo its q and equal to reduce_strict (mod_arith.h:58-72) of it -- the contract of
  *     intt_negacyclic_inplace (ntt.h:88-92) extended to the whole pipeline.  hp_dev_ext_prod_montgomery* returns lazy words
  *     (< 2q, rgsw.cpp:151) with hehub's residues.  Their transforms then run on error-free FP64
- *     products (hp_ntt_a.hip: 8 instead of 16 instructions per butterfly).  Needs every modulus of the chain below 2^50, a ring
+ *     products (hp_ntt_a.hip: 8 instead of 16 instructions per butterfly).  Needs every modulus of the chain below 2^50 and
+ *     exact under hehub's lazy fold (no prime a little above 2^k or well inside its octave: hp_tables.h level_a_modulus), a ring
  *     degree of 2^11 .. 2^15; a call whose chain does not qualify runs at level B.  Input words must be LAZY words of their limb
  *     (below 2 q: everything hehub or this engine produces is; hehub's own transforms take any u64, ntt.cpp:155-175, and level B
  *     reproduces that).  The precondition is CHECKED: every word a level-A kernel loads from a caller's row passes a range guard
@@ -191,7 +192,8 @@ int hp_dev_intt(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, size
  *   hp_dev_ntt_residues:  word == (ntt.cpp:145-176's lazy word) mod q, i.e. reduce_strict of it where that one is below 2q
  *   hp_dev_intt_residues: the words of intt_negacyclic_inplace (ntt.h:88-92 = lazy inverse + reduce_strict), bit for bit
  * Input words must be lazy words of their limb (below 2 q; checked: HP_ERANGE from the next hp_sync / hp_memcpy_d2h, see
- * hp_parity_level); N = 2^11 .. 2^15 and every modulus below 2^50, else HP_EUNSUPPORTED.  hp_dev_ntt / hp_dev_intt above stay bit-exact with the reference's lazy words. */
+ * hp_parity_level); N = 2^11 .. 2^15 and every modulus below 2^50 and exact under hehub's lazy fold (as hp_parity_level), else
+ * HP_EUNSUPPORTED.  hp_dev_ntt / hp_dev_intt above stay bit-exact with the reference's lazy words. */
 int hp_dev_ntt_residues(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, size_t batch, uint64_t *d_x);
 int hp_dev_intt_residues(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, size_t batch, uint64_t *d_x);
 /* rns.cpp:58-87 / :89-118 / :120-140 / :142-171 on u64[batch][L][N].  d_self may alias d_out. */

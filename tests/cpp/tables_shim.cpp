@@ -14,6 +14,13 @@ void tbl_consts(uint64_t q, uint64_t *out9) {
     uint64_t v[9] = {c.q, c.two_q, c.neg_q, c.mqinv, c.r64, c.r64h, c.barrett_c, c.k, c.fix};
     std::memcpy(out9, v, sizeof(v));
 }
+// hp::lazy_fold_bound: out = {wraps, m_delta lo, m_delta hi, word_end lo, word_end hi}
+void tbl_fold(uint64_t q, uint64_t x_in, size_t logn, uint64_t *out5) {
+    hp::FoldBound f = hp::lazy_fold_bound(hp::make_consts(q), x_in, logn);
+    uint64_t v[5] = {f.wraps ? 1u : 0u, (uint64_t)f.m_delta, (uint64_t)(f.m_delta >> 64), (uint64_t)f.word_end, (uint64_t)(f.word_end >> 64)};
+    std::memcpy(out5, v, sizeof(v));
+}
+int tbl_level_a(uint64_t q, uint64_t cmax, size_t logn) { return hp::level_a_modulus(hp::make_consts(q), cmax, logn) ? 1 : 0; }
 // out sizes (in pairs = 2 u64): fwd_ref N, inv_ref 2N, fwd_fast 31*2^a + 31*N/32, inv_fast 31 + 31*32 + 31*N/32
 void tbl_fwd_ref(uint64_t q, size_t logn, uint64_t *out) {
     std::vector<hp::Pair> t; hp::build_fwd_ref(q, logn, t); std::memcpy(out, t.data(), t.size() * sizeof(hp::Pair));

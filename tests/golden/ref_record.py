@@ -1,4 +1,4 @@
-"""The compiled reference as recorded results, for tests/test_oracle_vs_reference.py where the reference cannot be built.
+"""The compiled reference as recorded results, for tests/test_oracle_vs_reference.py and tests/test_moduli_edges.py where the reference cannot be built.
 
 Every call the tests make on the reference (`ref.<method>(*args)`) is keyed by a digest of the method name and its arguments; the
 value is a digest of what the reference returned (or the name of the exception it raised).  `Recorder` wraps the real reference and
@@ -70,6 +70,7 @@ class Recorder:
     def save(self, path=DIGESTS):
         with open(path, "w") as f:
             json.dump({"what": "digests of the compiled reference's results for the calls of tests/test_oracle_vs_reference.py "
+                               "and tests/test_moduli_edges.py "
                                "(tests/golden/ref_record.py, tests/golden/make_ref_digests.py)",
                        "calls": dict(sorted(self.table.items()))}, f, indent=0)
             f.write("\n")

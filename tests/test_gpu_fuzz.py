@@ -26,3 +26,13 @@ def test_random_cases_at_parity_level_a():
                          text=True, timeout=600)
     print(out.stdout[-2000:], out.stderr[-1000:])
     assert out.returncode == 0 and "fuzz ok" in out.stdout
+
+
+@pytest.mark.gpu
+def test_random_cases_on_edge_moduli():
+    """the level-B sweep with every modulus drawn from the families off the prime table (tests/moduli.py): primes just above 2^k,
+    inside their octave, 20 to 59 bits"""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "fuzz_parity.py"), "15", "31", "edges"], capture_output=True,
+                         text=True, timeout=600)
+    print(out.stdout[-2000:], out.stderr[-1000:])
+    assert out.returncode == 0 and "fuzz ok" in out.stdout

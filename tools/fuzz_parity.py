@@ -19,11 +19,15 @@ budget = float(sys.argv[1]) if len(sys.argv) > 1 else 120.0
 HKS = len(sys.argv) > 3 and sys.argv[3] == "hks"   # third argument "hks": only the hybrid key switch against its exact integer model
 LEVELA = len(sys.argv) > 3 and sys.argv[3] == "levela"   # "levela": the pipelines at parity level A (expected = the oracle's words mod q
                                                          # where the ring degree has tiled kernels, the raw words elsewhere) + residue transforms
+EDGES = len(sys.argv) > 3 and sys.argv[3] == "edges"   # "edges": moduli drawn from the families off the prime table (tests/moduli.py)
 seed0 = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 orc, eng = Oracle("orc"), Engine(0)
 if LEVELA:
     eng.set_parity_level("A")
 pool = P.P40 + P.P50          # every list prime supports 2N | q-1 up to N = 32768
+if EDGES:
+    import moduli as M
+    pool = sorted({q for q in M.ALL + [q for c in M.CHAINS.values() for q in c] if M.max_logn(q) >= 15})
 t0, cases, rs = time.time(), 0, np.random.RandomState(seed0)
 hist = {}
 
