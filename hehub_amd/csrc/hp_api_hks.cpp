@@ -8,7 +8,7 @@
 
 using namespace hpi;
 
-static int get_hks_consts(hp_ctx *ctx, const uint64_t *mext, size_t L, size_t k, size_t alpha, const HpHksConsts **out) {
+static int get_hks_consts(hp_ctx *ctx, const uint64_t *mext, size_t L, size_t k, size_t alpha, const HksEntry **out) {
     return contained(ctx, [&] {
         const size_t E = L + k, nd = (L + alpha - 1) / alpha;
         auto key = std::make_pair(std::vector<u64>(mext, mext + E), std::make_pair(k, alpha));
@@ -16,7 +16,7 @@ static int get_hks_consts(hp_ctx *ctx, const uint64_t *mext, size_t L, size_t k,
         if (it == ctx->hks.end()) {
             if (ctx->hks.size() >= MAX_HKS) {   // bounded cache (an entry is ~150 KB of device memory)
                 HIP_TRY(ctx, hipDeviceSynchronize());
-                for (auto &kv : ctx->hks) (void)hipFree(kv.second);
+                for (auto &kv : ctx->hks) (void)hipFree(kv.second.dev);
                 ctx->hks.clear();
             }
             typedef unsigned __int128 u128;
@@ -42,20 +42,13 @@ static int get_hks_consts(hp_ctx *ctx, const uint64_t *mext, size_t L, size_t k,
                     }
                 }
             }
+            HksEntry e;   // P^-1 and P mod q_i (the latter for the merged ModDown + rescale whatever k is): also kept on the host
+            if (!hks_limb_consts(mext, L, k, e.host)) return fail(ctx, HP_EINVAL, "moduli are not pairwise coprime");
             for (size_t i = 0; i < L; i++) {
-                u64 pm = 1 % mext[i];
-                for (size_t j = 0; j < k; j++) pm = (u64)((u128)pm * (mext[L + j] % mext[i]) % mext[i]);
-                if (pm == 0) return fail(ctx, HP_EINVAL, "moduli are not pairwise coprime");
-                c.pinv[i] = hp::inverse_mod_prime(pm, mext[i]) % mext[i];
-                c.pinv_h[i] = hp::harvey_quotient(c.pinv[i], mext[i]);
+                c.pinv[i] = e.host.pinv[i]; c.pinv_h[i] = e.host.pinv_h[i];
+                c.p_mod_q[i] = e.host.p_mod_q[i]; c.p_mod_q_h[i] = e.host.p_mod_q_h[i];
             }
             const uint64_t *pm = mext + L;
-            for (size_t i = 0; i < L; i++) {   // P mod q_i: needed by the merged ModDown + rescale whatever k is
-                u64 prod = 1 % mext[i];
-                for (size_t a = 0; a < k; a++) prod = (u64)((u128)prod * (pm[a] % mext[i]) % mext[i]);
-                c.p_mod_q[i] = prod;
-                c.p_mod_q_h[i] = hp::harvey_quotient(prod, mext[i]);
-            }
             if (k <= HP_HKS_MAX_ALPHA) {   // Garner tables of the one-kernel ModDown conversion
                 for (size_t a = 0; a < k; a++)
                     for (size_t b = 0; b < a; b++) {
@@ -77,23 +70,13 @@ static int get_hks_consts(hp_ctx *ctx, const uint64_t *mext, size_t L, size_t k,
                     }
                 }
             }
-            HpHksConsts *d = nullptr;
-            int rc = upload(ctx, &c, sizeof(c), (void **)&d);
+            int rc = upload(ctx, &c, sizeof(c), (void **)&e.dev);
             if (rc) return rc;
-            it = ctx->hks.emplace(key, d).first;
+            it = ctx->hks.emplace(key, std::move(e)).first;
         }
-        *out = it->second;
+        *out = &it->second;
         return (int)HP_OK;
     });
-}
-
-static u64 hc_host_pinv(hp_ctx *, const uint64_t *mext, size_t L, size_t k, size_t i, u64 *harvey) {
-    typedef unsigned __int128 u128;
-    u64 pm = 1 % mext[i];
-    for (size_t j = 0; j < k; j++) pm = (u64)((u128)pm * (mext[L + j] % mext[i]) % mext[i]);
-    const u64 inv = hp::inverse_mod_prime(pm, mext[i]) % mext[i];
-    *harvey = hp::harvey_quotient(inv, mext[i]);
-    return inv;
 }
 
 static size_t hks_ws_words(size_t n, size_t L, size_t k, size_t nd, size_t P) {
@@ -166,49 +149,38 @@ static int hks_front(hp_ctx *ctx, const Plan *plan, const HpHksConsts *hc, size_
 // Parity level A for the drops that end a hybrid key switch (round 6; DESIGN section 7 item 1 of round 5): the FP64 drop kernels of
 // hp_ntt_a.hip take them as they are -- their compile-time flavours 1 / 2 / 5 (no addend / addend on both polynomials / on polynomial 0)
 // for ModDown, flavour 6 (two drops in one transform) for ModDown merged with the rescale.  What differs from hehub's drops is only
-// that the transform's input rows already ARE the per-limb remainders: no centring, which the kernels do against a threshold -- a
-// threshold out of reach (2^62) switches it off.  Constants travel as pairs of doubles (v, RN(v / q)) like every level-A constant.
-static bool a_drop_shape(const u64 *addend, u32 add_mask) { return !addend || add_mask == 0 || add_mask == 3u || add_mask == 1u; }
-static void a_pair(u64 v, u64 q, u64 *bits, u64 *bits_h) {
-    *bits = hp::f64_bits((double)v);
-    *bits_h = hp::f64_bits((double)v / (double)q);
-}
-static void a_raw_rows(HpDropArgs &da) {
-    da.raw_input = 0;
-    da.dc.bgv = 0;
-    da.dc.q_last = hp::f64_bits(0.0);
-    da.dc.half_q_last = hp::f64_bits(4611686018427387904.0);   // 2^62: no word is ever "above half"
+// that the transform's input rows already ARE the per-limb remainders (hp_drop.h: a_raw_rows).
+static bool a_drop_shape(const Addend &add) { return add.mask == 0 || add.mask == 3u || add.mask == 1u; }
+
+// ModDown of the limbs [i0, i0 + cnt) with the transform of the remainders fused in: out = (ks - NTT(rem)) * P^-1 [+ addend]
+// (level A: the canonical residues of that)
+static int hks_down_fused(hp_ctx *ctx, const Plan *plan, const HksEntry *he, size_t logn, size_t L, size_t i0, size_t cnt, size_t P2,
+                          const u64 *rem, HpDropArgs &da, bool level_a, const uint64_t *mext, const char *what, const char *what_a) {
+    HpNttJob fj = batch_job(plan, logn, cnt, P2, rem + i0 * ((size_t)1 << logn), nullptr, L, 0, 0, 0);
+    fj.limbs = plan->d_limbs + i0;
+    hks_down_consts(he->host, i0, cnt, da);
+    ProfScope ps(ctx, "ntt_drop");
+    if (!level_a) return chk(ctx, hp_launch_ntt_fast_drop(fj, da, ctx->stream), what);
+    fj.limbs_a = plan->d_limbs_a + i0;
+    hks_down_consts_a(mext, i0, cnt, da);
+    return chk(ctx, hp_launch_ntt_a_drop(fj, da, ctx->stream), what_a);
 }
 
-static int hks_switch(hp_ctx *ctx, const Plan *plan, const HpHksConsts *hc, size_t logn, size_t L, size_t k, size_t alpha, size_t P,
-                      const u64 *pt, size_t pt_pstride, const u64 *key, const u64 *addend, size_t add_poly_stride,
-                      size_t add_ct_stride, u32 add_mask, const uint64_t *mext, u64 *out, Carver &cv) {
+static int hks_switch(hp_ctx *ctx, const Plan *plan, const HksEntry *he, size_t logn, size_t L, size_t k, size_t alpha, size_t P,
+                      const u64 *pt, size_t pt_pstride, const u64 *key, const Addend &add, const uint64_t *mext, u64 *out, Carver &cv) {
     const size_t n = (size_t)1 << logn, E = L + k;
     u64 *ks, *rem;
     int rc;
-    if ((rc = hks_front(ctx, plan, hc, logn, L, k, alpha, P, pt, pt_pstride, key, mext, &ks, &rem, cv))) return rc;
-    // transform of the remainders with the rest of ModDown fused into its stores: out = (x - NTT(rem)) * P^-1 [+ addend]
+    if ((rc = hks_front(ctx, plan, he->dev, logn, L, k, alpha, P, pt, pt_pstride, key, mext, &ks, &rem, cv))) return rc;
     if (fused_drop_ok(ctx, logn)) {
-        HpNttJob fj = batch_job(plan, logn, L, 2 * P, rem, nullptr, L, 0, 0, 0);
-        HpDropArgs da;
-        memset(&da, 0, sizeof(da));
-        da.raw_input = 1;
-        for (size_t i = 0; i < L; i++) { da.dc.inv[i] = hc_host_pinv(ctx, mext, L, k, i, &da.dc.inv_h[i]); }
-        da.x = ks; da.L = (u32)E; da.addend = addend; da.add_poly_stride = (u32)add_poly_stride; da.add_ct_stride = (u32)add_ct_stride;
-        da.add_mask = addend ? add_mask : 0u; da.out = out; da.out_stride = (u32)L;
-        ProfScope ps(ctx, "ntt_drop");
-        if (ctx->cur_a && a_drop_shape(addend, add_mask)) {   // out = canonical residues of (ks - NTT(rem)) P^-1 [+ addend]
-            fj.limbs_a = plan->d_limbs_a;
-            a_raw_rows(da);
-            for (size_t i = 0; i < L; i++) a_pair(da.dc.inv[i], mext[i], &da.dc.inv[i], &da.dc.inv_h[i]);
-            return chk(ctx, hp_launch_ntt_a_drop(fj, da, ctx->stream), "hks fused ModDown (level A)");
-        }
-        return chk(ctx, hp_launch_ntt_fast_drop(fj, da, ctx->stream), "hks fused ModDown");
+        HpDropArgs da = drop_args(ks, E, add, out, L);
+        return hks_down_fused(ctx, plan, he, logn, L, 0, L, 2 * P, rem, da, ctx->cur_a && a_drop_shape(add), mext, "hks fused ModDown",
+                              "hks fused ModDown (level A)");
     }
     if ((rc = run_ntt(ctx, batch_job(plan, logn, L, 2 * P, rem, rem, L, L, 0, 0)))) return rc;
     ProfScope ps(ctx, "hks_down_fin");
-    return chk(ctx, hp_launch_hks_down_fin(plan->d_limbs, hc, (u32)L, (u32)n, (u32)(2 * P), ks, rem, addend, (u32)add_poly_stride,
-                                           (u32)add_ct_stride, add_mask, out, ctx->stream), "hks_down_fin");
+    return chk(ctx, hp_launch_hks_down_fin(plan->d_limbs, he->dev, (u32)L, (u32)n, (u32)(2 * P), ks, rem, add.rows, add.poly_stride,
+                                           add.ct_stride, add.mask, out, ctx->stream), "hks_down_fin");
 }
 
 static int hks_args_ok(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, size_t batch) {
@@ -229,14 +201,14 @@ extern "C" int hp_dev_hks_switch(hp_ctx *ctx, size_t logn, size_t L, size_t k, s
     if (rc) return rc;
     const Plan *plan;
     if ((rc = get_plan(ctx, logn, moduli_ext, L + k, true, &plan))) return rc;
-    const HpHksConsts *hc;
-    if ((rc = get_hks_consts(ctx, moduli_ext, L, k, alpha, &hc))) return rc;
+    const HksEntry *he;
+    if ((rc = get_hks_consts(ctx, moduli_ext, L, k, alpha, &he))) return rc;
     LevelScope lvl(ctx, plan);   // level A: the transforms of the lifted digits and the coefficient rows on the FP64 kernels
     if (lvl.rc) return lvl.rc;
     const size_t n = (size_t)1 << logn, nd = (L + alpha - 1) / alpha;
     if ((rc = ws_reserve(ctx, hks_ws_words(n, L, k, nd, batch) * 8))) return rc;
     Carver cv(ctx->ws);
-    return hks_switch(ctx, plan, hc, logn, L, k, alpha, batch, pt, L, key, nullptr, 0, 0, 0, moduli_ext, out, cv);
+    return hks_switch(ctx, plan, he, logn, L, k, alpha, batch, pt, L, key, Addend(), moduli_ext, out, cv);
 }
 
 // ckks rotate / conjugate with a hybrid key: moved = gather(ct); out = hks_switch(moved[1]); out[0] += moved[0]
@@ -250,26 +222,16 @@ static int dev_hks_automorphism(hp_ctx *ctx, size_t logn, size_t L, size_t k, si
     if (!conj && step >= ((size_t)1 << 17)) return fail(ctx, HP_EINVAL, "rotation step out of range");
     const Plan *plan;
     if ((rc = get_plan(ctx, logn, mext, L + k, true, &plan))) return rc;
-    const HpHksConsts *hc;
-    if ((rc = get_hks_consts(ctx, mext, L, k, alpha, &hc))) return rc;
+    const HksEntry *he;
+    if ((rc = get_hks_consts(ctx, mext, L, k, alpha, &he))) return rc;
     LevelScope lvl(ctx, plan);
     if (lvl.rc) return lvl.rc;
     const size_t n = (size_t)1 << logn, nd = (L + alpha - 1) / alpha;
     if ((rc = ws_reserve(ctx, (padded(batch * 2 * L * n) / 8 + hks_ws_words(n, L, k, nd, batch)) * 8))) return rc;
     Carver cv(ctx->ws);
     u64 *moved = cv.take(batch * 2 * L * n);
-    {
-        ProfScope ps(ctx, "elem");
-        if (conj) {
-            rc = chk(ctx, hp_launch_reverse((u32)n, (u32)(batch * 2 * L), ct, moved, ctx->stream), "involution");
-        } else {
-            const u32 *perm;
-            if ((rc = get_cycle_perm(ctx, logn, step, &perm))) return rc;
-            rc = chk(ctx, hp_launch_gather(perm, (u32)n, (u32)(batch * 2 * L), ct, moved, ctx->stream), "cycle");
-        }
-        if (rc) return rc;
-    }
-    return hks_switch(ctx, plan, hc, logn, L, k, alpha, batch, moved + L * n, 2 * L, key, moved, L, 2 * L, 1, mext, out, cv);
+    if ((rc = move_rows(ctx, logn, batch * 2 * L, conj, step, ct, moved))) return rc;
+    return hks_switch(ctx, plan, he, logn, L, k, alpha, batch, moved + L * n, 2 * L, key, Addend(moved, L, 2 * L, 1), mext, out, cv);
 }
 extern "C" int hp_dev_ckks_rotate_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t batch,
                            size_t step, const uint64_t *ct, const uint64_t *rot_key, uint64_t *out) {
@@ -292,8 +254,8 @@ extern "C" int hp_dev_ckks_mult_relin_rescale_hks(hp_ctx *ctx, size_t logn, size
     if (L < 2) return fail(ctx, HP_EINVAL, "Unable to drop the only one prime.");
     const Plan *plan;
     if ((rc = get_plan(ctx, logn, moduli_ext, L + k, true, &plan))) return rc;
-    const HpHksConsts *hc;
-    if ((rc = get_hks_consts(ctx, moduli_ext, L, k, alpha, &hc))) return rc;
+    const HksEntry *he;
+    if ((rc = get_hks_consts(ctx, moduli_ext, L, k, alpha, &he))) return rc;
     LevelScope lvl(ctx, plan);
     if (lvl.rc) return lvl.rc;
     const size_t n = (size_t)1 << logn, nd = (L + alpha - 1) / alpha;
@@ -313,28 +275,15 @@ extern "C" int hp_dev_ckks_mult_relin_rescale_hks(hp_ctx *ctx, size_t logn, size
         // so: ModDown of limb L-1 alone -> its coefficients -> rem_i += P centre_i(c) -> one fused transform over limbs 0..L-2.
         // The same residues as the two-step composition below (another lazy representative of them).
         const size_t P2 = 2 * batch, E = L + k;
+        const Addend add(quad, L, 3 * L, 3);
         u64 *ks, *rem;
-        if ((rc = hks_front(ctx, plan, hc, logn, L, k, alpha, batch, quad + 2 * L * n, 3 * L, key, moduli_ext, &ks, &rem, cv))) return rc;
+        if ((rc = hks_front(ctx, plan, he->dev, logn, L, k, alpha, batch, quad + 2 * L * n, 3 * L, key, moduli_ext, &ks, &rem, cv))) return rc;
         u64 *r_last = cv.take(P2 * n), *c_last = cv.take(P2 * n);
-        HpDropArgs da;
         {
-            HpNttJob fj = batch_job(plan, logn, 1, P2, rem + (L - 1) * n, nullptr, L, 0, 0, 0);
-            fj.limbs = plan->d_limbs + (L - 1);
-            memset(&da, 0, sizeof(da));
-            da.raw_input = 1;
-            da.dc.inv[0] = hc_host_pinv(ctx, moduli_ext, L, k, L - 1, &da.dc.inv_h[0]);
-            da.x = ks + (L - 1) * n; da.L = (u32)E; da.addend = quad + (L - 1) * n; da.add_poly_stride = (u32)L;
-            da.add_ct_stride = (u32)(3 * L); da.add_mask = 3u; da.out = r_last; da.out_stride = 1;
-            ProfScope ps(ctx, "ntt_drop");
-            if (ctx->cur_a) {
-                fj.limbs_a = plan->d_limbs_a + (L - 1);
-                a_raw_rows(da);
-                a_pair(da.dc.inv[0], moduli_ext[L - 1], &da.dc.inv[0], &da.dc.inv_h[0]);
-                rc = chk(ctx, hp_launch_ntt_a_drop(fj, da, ctx->stream), "hks ModDown of the last limb (level A)");
-            } else {
-                rc = chk(ctx, hp_launch_ntt_fast_drop(fj, da, ctx->stream), "hks ModDown of the last limb");
-            }
-            if (rc) return rc;
+            HpDropArgs da = drop_args(ks + (L - 1) * n, E, add.from((L - 1) * n), r_last, 1);
+            if ((rc = hks_down_fused(ctx, plan, he, logn, L, L - 1, 1, P2, rem, da, ctx->cur_a, moduli_ext, "hks ModDown of the last limb",
+                                     "hks ModDown of the last limb (level A)")))
+                return rc;
         }
         {
             HpNttJob lj = batch_job(plan, logn, 1, P2, r_last, c_last, 1, 1, 1, 1);
@@ -345,48 +294,25 @@ extern "C" int hp_dev_ckks_mult_relin_rescale_hks(hp_ctx *ctx, size_t logn, size
         const bool in_loads = !ctx->hks_combine_kernel;   // HP_HKS_COMBINE_KERNEL: the combination as its own kernel
         if (!in_loads) {
             ProfScope ps(ctx, "hks_combine");
-            if ((rc = chk(ctx, hp_launch_hks_combine(plan->d_limbs, hc, (u32)L, (u32)n, (u32)P2, c_last, rem, ctx->stream), "hks_combine")))
+            if ((rc = chk(ctx, hp_launch_hks_combine(plan->d_limbs, he->dev, (u32)L, (u32)n, (u32)P2, c_last, rem, ctx->stream), "hks_combine")))
                 return rc;
         }
         HpNttJob fj = batch_job(plan, logn, L - 1, P2, rem, nullptr, L, 0, 0, 0);
-        memset(&da, 0, sizeof(da));
-        da.raw_input = 1;
-        da.fin_on = 1;
-        const u64 q_last = moduli_ext[L - 1];
-        if (in_loads) { da.comb = c_last; da.comb_half = q_last / 2; }
-        for (size_t i = 0; i + 1 < L; i++) {
-            u64 pm = 1 % moduli_ext[i];
-            for (size_t j = 0; j < k; j++) pm = (u64)((unsigned __int128)pm * (moduli_ext[L + j] % moduli_ext[i]) % moduli_ext[i]);
-            da.comb_mul[i] = pm; da.comb_mul_h[i] = hp::harvey_quotient(pm, moduli_ext[i]); da.comb_r[i] = q_last % moduli_ext[i];
-            da.dc.inv[i] = hc_host_pinv(ctx, moduli_ext, L, k, i, &da.dc.inv_h[i]);
-            da.fin[i] = hp::inverse_mod_prime(q_last % moduli_ext[i], moduli_ext[i]) % moduli_ext[i];
-            da.fin_h[i] = hp::harvey_quotient(da.fin[i], moduli_ext[i]);
-        }
-        da.x = ks; da.L = (u32)E; da.addend = quad; da.add_poly_stride = (u32)L; da.add_ct_stride = (u32)(3 * L); da.add_mask = 3u;
-        da.out = out; da.out_stride = (u32)(L - 1);
+        HpDropArgs da = drop_args(ks, E, add, out, L - 1);
+        hks_down_rescale_consts(he->host, moduli_ext, L, in_loads ? c_last : nullptr, da);
         ProfScope ps(ctx, "ntt_drop");
         if (ctx->cur_a && in_loads) {
             // the two-drops flavour of hp_ntt_a.hip (DropPre2A has the algebra): z = ((A x + a) - NTT(m c1 + c2)) B with x = ks, a = quad,
             // c1 = the remainders (as they are), c2 = the centred coefficients of the relinearised last limb, A = m = P^-1, B = q_last^-1 --
             // by linearity the level-B line above: ((ks - NTT(rem + P centre(c))) P^-1 + quad) q_last^-1
             fj.limbs_a = plan->d_limbs_a;
-            a_raw_rows(da);
-            da.fin_on = 0;
-            da.q2_last = hp::f64_bits((double)q_last);
-            da.half_q2_last = hp::f64_bits((double)(q_last / 2));
-            for (size_t i = 0; i + 1 < L; i++) {
-                const u64 q = moduli_ext[i], A = da.dc.inv[i], B = da.fin[i];
-                a_pair(A, q, &da.dc.inv[i], &da.dc.inv_h[i]);
-                a_pair(A, q, &da.dc.t[i], &da.dc.t_h[i]);
-                a_pair(1 % q, q, &da.comb_mul[i], &da.comb_mul_h[i]);
-                a_pair(B, q, &da.dc.qlt[i], &da.dc.qlt_h[i]);
-            }
+            hks_down_rescale_consts_a(moduli_ext, L, da);
             return chk(ctx, hp_launch_ntt_a_drop(fj, da, ctx->stream), "hks fused ModDown + rescale (level A)");
         }
         return chk(ctx, hp_launch_ntt_fast_drop(fj, da, ctx->stream), "hks fused ModDown + rescale");
     }
-    if ((rc = hks_switch(ctx, plan, hc, logn, L, k, alpha, batch, quad + 2 * L * n, 3 * L, key, quad, L, 3 * L, 3, moduli_ext, lin, cv)))
+    if ((rc = hks_switch(ctx, plan, he, logn, L, k, alpha, batch, quad + 2 * L * n, 3 * L, key, Addend(quad, L, 3 * L, 3), moduli_ext, lin, cv)))
         return rc;
-    return drop_last(ctx, plan, logn, L, 2 * batch, false, 0, lin, nullptr, 0, 0, 0, out, cv);
+    return drop_last(ctx, plan, logn, L, 2 * batch, false, 0, lin, Addend(), out, cv);
 }
 

@@ -129,127 +129,79 @@ size_t drop_ws_words(size_t n, size_t L, size_t P2) { return padded(P2 * n) / 8 
 
 namespace {
 
-void make_drop_consts(const Plan *plan, size_t L, bool bgv, u64 t, HpDropConsts &dc) {
-    const u64 q_last = plan->consts[L - 1].q;
-    memset(&dc, 0, sizeof(dc));
-    dc.q_last = q_last;
-    dc.half_q_last = q_last / 2;
-    dc.bgv = bgv ? 1 : 0;
-    for (size_t k = 0; k + 1 < L; k++) {
-        const u64 q = plan->consts[k].q;
-        dc.r[k] = q_last % q;
-        const u64 inv = hp::inverse_mod_prime(q_last, q) % q;
-        dc.inv[k] = inv;
-        dc.inv_h[k] = hp::harvey_quotient(inv, q);
-        if (bgv) {
-            dc.t[k] = t % q;
-            dc.t_h[k] = hp::harvey_quotient(dc.t[k], q);
-            dc.qlt[k] = (q_last % t) % q;
-            dc.qlt_h[k] = hp::harvey_quotient(dc.qlt[k], q);
-        }
-    }
-}
-
 // clast[p2] = strict(INTT_{q_last}(x[p2][last]))  (BGV: times t^-1 before the strict reduction):
 // a one-limb batch whose rows are the last limbs of the P2 polynomials
-int drop_coeffs(hp_ctx *ctx, const Plan *plan, size_t logn, size_t L, size_t P2, bool bgv, u64 t, const u64 *x, u64 *clast) {
+HpNttJob last_limb_job(const hp_ctx *ctx, const Plan *plan, size_t logn, size_t L, size_t P2, bool bgv, u64 t, const u64 *x, u64 *clast) {
     const size_t n = (size_t)1 << logn;
-    const u64 q_last = plan->consts[L - 1].q;
-    HpNttJob lj;
-    memset(&lj, 0, sizeof(lj));
-    lj.limbs = plan->d_limbs + (L - 1); lj.src = x + (L - 1) * n; lj.dst = clast; lj.logn = (u32)logn; lj.L = 1;
-    lj.P = (u32)P2; lj.src_pstride = (u32)L; lj.dst_pstride = 1; lj.src_kstride = 1; lj.W = (u32)P2; lj.mode = HP_NTT_BATCH;
-    lj.inverse = 1; lj.strict = 1;
+    HpNttJob lj = batch_job(plan, logn, 1, P2, x + (L - 1) * n, clast, L, 1, 1, 1);
+    lj.limbs = plan->d_limbs + (L - 1);
     if (ctx->cur_a) lj.limbs_a = plan->d_limbs_a + (L - 1);
     if (bgv) {
-        const u64 s = hp::inverse_mod_prime(t, q_last) % q_last;
-        lj.post_scalar = s;
-        lj.post_scalar_h = hp::harvey_quotient(s, q_last);
-        if (lj.limbs_a) {
-            lj.post_scalar = hp::f64_bits((double)s);
-            lj.post_scalar_h = hp::f64_bits((double)s / (double)q_last);
-        }
+        drop_post_scalar(t, plan->consts[L - 1].q, lj.limbs_a != nullptr, lj.post_scalar, lj.post_scalar_h);
         lj.use_post_scalar = 1;
     }
-    return run_ntt(ctx, lj);
+    return lj;
+}
+int drop_coeffs(hp_ctx *ctx, const Plan *plan, size_t logn, size_t L, size_t P2, bool bgv, u64 t, const u64 *x, u64 *clast) {
+    return run_ntt(ctx, last_limb_job(ctx, plan, logn, L, P2, bgv, t, x, clast));
+}
+
+// the fused drop's transform: kc limbs from `first` on, every one reading the same coefficient row of its polynomial
+HpNttJob drop_job(const hp_ctx *ctx, const Plan *plan, size_t logn, size_t first, size_t kc, size_t P2, const u64 *clast, u64 *scratch,
+                  bool level_a) {
+    HpNttJob fj = batch_job(plan, logn, kc, P2, clast, scratch, 1, scratch ? kc : 0, 0, 0);
+    fj.limbs = plan->d_limbs + first;
+    if (level_a) fj.limbs_a = plan->d_limbs_a + first;
+    fj.src_kstride = 0;
+    if (!scratch) fj.pair_moduli = (u32)std::min((size_t)ctx->drop_group, kc);
+    return fj;
 }
 
 // out[k] = ((x[k] - NTT_k(centre(barrett_k(clast)))) * inv_k) [* (q_last mod t)] [+ addend[k]] for the limbs k in [k0, k1)
 // of the L-1 that remain.  rem: workspace of P2*(k1-k0)*n words (unused by the fused tiled path).
-int drop_apply(hp_ctx *ctx, const Plan *plan, size_t logn, size_t L, size_t P2, size_t k0, size_t k1, const HpDropConsts &dc0,
-               const u64 *x, const u64 *clast, bool clast_strict, const u64 *addend, size_t add_poly_stride, size_t add_ct_stride,
-               u32 add_mask, u64 *out, u64 *rem) {
+int drop_apply(hp_ctx *ctx, const Plan *plan, size_t logn, size_t L, size_t P2, size_t k0, size_t k1, bool bgv, u64 t, const u64 *x,
+               const u64 *clast, bool clast_strict, const Addend &add0, u64 *out, u64 *rem) {
     // clast_strict: the caller vouches that every word of clast is below q_last (drop_last: it has just been written by a
     // strict inverse transform).  Rows handed in over the C ABI get the full Barrett reduction, which is right for any u64.
     const size_t n = (size_t)1 << logn, kc = k1 - k0;
     if (kc == 0) return HP_OK;
-    // shift everything that is indexed by the limb number to the first limb of the range
-    HpDropConsts dc = dc0;
-    for (size_t k = 0; k < kc; k++) {
-        dc.r[k] = dc0.r[k0 + k]; dc.inv[k] = dc0.inv[k0 + k]; dc.inv_h[k] = dc0.inv_h[k0 + k];
-        dc.t[k] = dc0.t[k0 + k]; dc.t_h[k] = dc0.t_h[k0 + k]; dc.qlt[k] = dc0.qlt[k0 + k]; dc.qlt_h[k] = dc0.qlt_h[k0 + k];
-    }
+    // everything that is indexed by the limb number starts at the first limb of the range
+    const hp::ModConsts *chain = plan->consts.data();
     const HpLimb *limbs = plan->d_limbs + k0;
-    x += k0 * n;
-    out += k0 * n;
-    if (addend) addend += k0 * n;
+    const Addend add = add0.from(k0 * n);
+    HpDropArgs da = drop_args(x + k0 * n, L, add, out + k0 * n, L - 1);
+    drop_consts(chain, L, k0, k1, bgv, t, da.dc);
+    const bool few = split_ok(ctx, logn, kc * P2) && !ctx->cur_a;
     int rc;
     // tiled sizes: Barrett + centring fused into the remainder NTT's loads, (x - rem)*inv [+ addend] into its stores
     // (not for a launch of a few limbs at level B: three short launches around the SPLIT transform beat one 45 us workgroup per limb)
-    if (fused_drop_ok(ctx, logn) && !(split_ok(ctx, logn, kc * P2) && !ctx->cur_a)) {
-        HpNttJob fj = batch_job(plan, logn, kc, P2, clast, nullptr, 1, 0, 0, 0);
-        fj.limbs = limbs;
-        fj.src_kstride = 0;
-        fj.pair_moduli = (u32)ctx->drop_group;
-        if (fj.pair_moduli > kc) fj.pair_moduli = (u32)kc;
-        HpDropArgs da;
-        memset(&da, 0, sizeof(da));
-        da.dc = dc; da.x = x; da.L = (u32)L; da.addend = addend; da.add_poly_stride = (u32)add_poly_stride;
-        da.add_ct_stride = (u32)add_ct_stride; da.add_mask = add_mask; da.out = out; da.out_stride = (u32)(L - 1);
-        da.small_rem = clast_strict ? 1 : 0;   // rescaling.cpp:54-58: strict_barrett_{q_k}(c), c < q_last -- one conditional subtraction when q_last <= 2 q_k
-        for (size_t k = k0; k < k1; k++)
-            if (plan->consts[L - 1].q > 2 * plan->consts[k].q) da.small_rem = 0;
+    if (fused_drop_ok(ctx, logn) && !few) {
+        da.small_rem = clast_strict ? drop_small_rem(chain, L, k0, k1) : 0;
         ProfScope ps(ctx, "ntt_drop");   // its own family: a different kernel (k_ntt_fwd_drop) with 2-3x the bytes of a plain transform
-        const bool a_shape = add_mask == 0 || !addend || add_mask == 3u || (add_mask == 1u && !dc.bgv);
-        if (ctx->cur_a && clast_strict && a_shape) {
-            // level A: the same launch on the FP64 kernel; every constant as the pair of doubles (v, RN(v / q_k))
-            fj.limbs_a = plan->d_limbs_a + k0;
-            const double ql = (double)dc.q_last;
-            da.dc.q_last = hp::f64_bits(ql);
-            da.dc.half_q_last = hp::f64_bits((double)dc.half_q_last);
-            for (size_t k = 0; k < kc; k++) {
-                const double qk = (double)plan->consts[k0 + k].q;
-                da.dc.inv[k] = hp::f64_bits((double)dc.inv[k]); da.dc.inv_h[k] = hp::f64_bits((double)dc.inv[k] / qk);
-                da.dc.t[k] = hp::f64_bits((double)dc.t[k]); da.dc.t_h[k] = hp::f64_bits((double)dc.t[k] / qk);
-                da.dc.qlt[k] = hp::f64_bits((double)dc.qlt[k]); da.dc.qlt_h[k] = hp::f64_bits((double)dc.qlt[k] / qk);
-            }
-            return chk(ctx, hp_launch_ntt_a_drop(fj, da, ctx->stream), "fused drop NTT (level A)");
+        const bool a_shape = add.mask == 0 || add.mask == 3u || (add.mask == 1u && !bgv);
+        if (ctx->cur_a && clast_strict && a_shape) {   // level A: the same launch on the FP64 kernel
+            drop_consts_to_a(chain, k0, k1, da.dc);
+            return chk(ctx, hp_launch_ntt_a_drop(drop_job(ctx, plan, logn, k0, kc, P2, clast, nullptr, true), da, ctx->stream),
+                       "fused drop NTT (level A)");
         }
-        return chk(ctx, hp_launch_ntt_fast_drop(fj, da, ctx->stream), "fused drop NTT");
+        return chk(ctx, hp_launch_ntt_fast_drop(drop_job(ctx, plan, logn, k0, kc, P2, clast, nullptr, false), da, ctx->stream), "fused drop NTT");
     }
-    if (split_ok(ctx, logn, kc * P2) && !ctx->cur_a && !ctx->no_fused_drop) {
+    if (few && !ctx->no_fused_drop) {
         // a few limbs: the fused drop around the SPLIT transform (two launches of small workgroups; `rem` holds the rows between them)
-        HpNttJob sj = batch_job(plan, logn, kc, P2, clast, rem, 1, kc, 0, 0);
-        sj.limbs = limbs;
-        sj.src_kstride = 0;
-        HpDropArgs da;
-        memset(&da, 0, sizeof(da));
-        da.dc = dc; da.x = x; da.L = (u32)L; da.addend = addend; da.add_poly_stride = (u32)add_poly_stride;
-        da.add_ct_stride = (u32)add_ct_stride; da.add_mask = add_mask; da.out = out; da.out_stride = (u32)(L - 1);
         ProfScope ps(ctx, "ntt_drop");
-        return chk(ctx, hp_launch_ntt_split_drop(sj, da, ctx->stream), "fused drop NTT (split)");
+        return chk(ctx, hp_launch_ntt_split_drop(drop_job(ctx, plan, logn, k0, kc, P2, clast, rem, false), da, ctx->stream), "fused drop NTT (split)");
     }
     {
         ProfScope ps(ctx, "drop_rem");
-        if ((rc = chk(ctx, hp_launch_drop_rem(limbs, dc, (u32)kc, (u32)n, (u32)P2, clast, rem, ctx->stream), "drop_rem"))) return rc;
+        if ((rc = chk(ctx, hp_launch_drop_rem(limbs, da.dc, (u32)kc, (u32)n, (u32)P2, clast, rem, ctx->stream), "drop_rem"))) return rc;
     }
     HpNttJob rj = batch_job(plan, logn, kc, P2, rem, rem, kc, kc, 0, 0);
     rj.limbs = limbs;
     if ((rc = run_ntt(ctx, rj))) return rc;
     {
         ProfScope ps(ctx, "drop_fin");
-        rc = chk(ctx, hp_launch_drop_fin(limbs, dc, (u32)L, (u32)kc, (u32)n, (u32)P2, x, rem, addend, (u32)add_poly_stride,
-                                         (u32)add_ct_stride, add_mask, out, ctx->stream), "drop_fin");
+        rc = chk(ctx, hp_launch_drop_fin(limbs, da.dc, (u32)L, (u32)kc, (u32)n, (u32)P2, da.x, rem, add.rows, add.poly_stride, add.ct_stride,
+                                         add.mask, da.out, ctx->stream), "drop_fin");
     }
     return rc;
 }
@@ -260,96 +212,53 @@ int drop_apply(hp_ctx *ctx, const Plan *plan, size_t logn, size_t L, size_t P2, 
 // for the limbs k < L - 1, and of the limb L - 1 only the coefficients the second drop needs (one inverse launch, also by linearity).
 bool two_drops_ok(const hp_ctx *ctx, size_t logn, size_t L) { return ctx->cur_a && !ctx->no_double_drop && fused_drop_ok(ctx, logn) && L >= 2; }
 int drop_two_last_a(hp_ctx *ctx, const Plan *plan, size_t logn, size_t L, size_t P2, bool bgv, u64 t1, u64 t2, const u64 *ext,
-                    const u64 *addend, size_t add_poly_stride, size_t add_ct_stride, u64 *out, Carver &cv) {
-    const size_t n = (size_t)1 << logn;
-    HpDropConsts dc1, dc2;
-    make_drop_consts(plan, L + 1, bgv, t1, dc1);
-    make_drop_consts(plan, L, bgv, t2, dc2);
+                    const Addend &add, u64 *out, Carver &cv) {
+    const size_t n = (size_t)1 << logn, kl = L - 1;
     u64 *cp = cv.take(P2 * n), *cq = cv.take(P2 * n);
     int rc;
-    auto mulmod = [](u64 a, u64 b, u64 q) { return (u64)(((unsigned __int128)a * b) % q); };
     if ((rc = drop_coeffs(ctx, plan, logn, L + 1, P2, bgv, t1, ext, cp))) return rc;
+    HpDropArgs da = drop_args(ext, L + 1, Addend(add.rows, add.poly_stride, add.ct_stride, 3), out, L - 1);
+    da.comb = cq;
+    HpInvMixArgs mx;
+    memset(&mx, 0, sizeof(mx));
+    mx.add = add.rows + kl * n; mx.add_poly_stride = add.poly_stride; mx.add_ct_stride = add.ct_stride;
+    mx.cprev = cp;
+    two_drop_consts(plan->consts.data(), L, bgv, t1, t2, da, mx);
     {
         // cq: the strict coefficients modulo q' of y_{L-1} = A' ext_{L-1} + addend_{L-1} - NTT(K cp) [times t2^-1], which are
         // INTT(A' ext_{L-1} + addend_{L-1}) - K cp: one inverse launch (k_ntt_inv_mix_a), y_{L-1} itself is never formed
-        const size_t kl = L - 1;
-        const u64 q2 = plan->consts[kl].q;
-        u64 A = dc1.inv[kl], K = A;
-        if (bgv) {
-            A = mulmod(A, dc1.qlt[kl], q2);
-            K = mulmod(A, dc1.t[kl], q2);
-        }
-        HpNttJob lj;
-        memset(&lj, 0, sizeof(lj));
-        lj.limbs = plan->d_limbs + kl; lj.limbs_a = plan->d_limbs_a + kl; lj.src = ext + kl * n; lj.dst = cq; lj.logn = (u32)logn; lj.L = 1;
-        lj.P = (u32)P2; lj.src_pstride = (u32)(L + 1); lj.dst_pstride = 1; lj.src_kstride = 1; lj.W = (u32)P2; lj.mode = HP_NTT_BATCH;
-        lj.inverse = 1; lj.strict = 1;
-        if (bgv) {
-            const u64 s = hp::inverse_mod_prime(t2, q2) % q2;
-            lj.post_scalar = hp::f64_bits((double)s);
-            lj.post_scalar_h = hp::f64_bits((double)s / (double)q2);
-            lj.use_post_scalar = 1;
-        }
-        HpInvMixArgs mx;
-        memset(&mx, 0, sizeof(mx));
-        mx.add = addend + kl * n; mx.add_poly_stride = (u32)add_poly_stride; mx.add_ct_stride = (u32)add_ct_stride;
-        mx.A = hp::f64_bits((double)A); mx.A_h = hp::f64_bits((double)A / (double)q2);
-        mx.K = hp::f64_bits((double)K); mx.K_h = hp::f64_bits((double)K / (double)q2);
-        mx.cprev = cp; mx.prev_q = hp::f64_bits((double)dc1.q_last); mx.prev_half = hp::f64_bits((double)dc1.half_q_last);
+        HpNttJob lj = last_limb_job(ctx, plan, logn, L, P2, bgv, t2, ext, cq);
+        lj.src_pstride = (u32)(L + 1);   // (rows of ext)
         ProfScope ps(ctx, "intt");
         if ((rc = chk(ctx, hp_launch_ntt_a_inv_mix(lj, mx, ctx->stream), "inverse NTT of the combined limb (level A)"))) return rc;
     }
-    const size_t kc = L - 1;
-    if (kc == 0) return HP_OK;
-    HpNttJob fj = batch_job(plan, logn, kc, P2, cp, nullptr, 1, 0, 0, 0);
-    fj.limbs = plan->d_limbs;
-    fj.limbs_a = plan->d_limbs_a;
-    fj.src_kstride = 0;
-    fj.pair_moduli = (u32)ctx->drop_group;
-    if (fj.pair_moduli > kc) fj.pair_moduli = (u32)kc;
-    HpDropArgs da;
-    memset(&da, 0, sizeof(da));
-    da.x = ext; da.L = (u32)(L + 1); da.addend = addend; da.add_poly_stride = (u32)add_poly_stride; da.add_ct_stride = (u32)add_ct_stride;
-    da.add_mask = 3; da.out = out; da.out_stride = (u32)(L - 1);
-    da.comb = cq;
-    da.dc.bgv = bgv ? 1 : 0;
-    da.dc.q_last = hp::f64_bits((double)dc1.q_last);
-    da.dc.half_q_last = hp::f64_bits((double)dc1.half_q_last);
-    da.q2_last = hp::f64_bits((double)dc2.q_last);
-    da.half_q2_last = hp::f64_bits((double)dc2.half_q_last);
-    for (size_t k = 0; k < kc; k++) {
-        const u64 q = plan->consts[k].q;
-        const double qd = (double)q;
-        // A = p^-1 [(p mod t1)], m = A [t1], m2 = 1 [t2], B = q'^-1 [(q' mod t2)]     (bracketed factors: BGV)
-        u64 A = dc1.inv[k], m = A, m2 = 1 % q, B = dc2.inv[k];
-        if (bgv) {
-            A = mulmod(A, dc1.qlt[k], q);
-            m = mulmod(A, dc1.t[k], q);
-            m2 = dc2.t[k];
-            B = mulmod(B, dc2.qlt[k], q);
-        }
-        da.dc.inv[k] = hp::f64_bits((double)A); da.dc.inv_h[k] = hp::f64_bits((double)A / qd);
-        da.dc.t[k] = hp::f64_bits((double)m); da.dc.t_h[k] = hp::f64_bits((double)m / qd);
-        da.comb_mul[k] = hp::f64_bits((double)m2); da.comb_mul_h[k] = hp::f64_bits((double)m2 / qd);
-        da.dc.qlt[k] = hp::f64_bits((double)B); da.dc.qlt_h[k] = hp::f64_bits((double)B / qd);
-    }
+    if (kl == 0) return HP_OK;
     ProfScope ps(ctx, "ntt_drop");
-    return chk(ctx, hp_launch_ntt_a_drop(fj, da, ctx->stream), "fused double drop NTT (level A)");
+    return chk(ctx, hp_launch_ntt_a_drop(drop_job(ctx, plan, logn, 0, kl, P2, cp, nullptr, true), da, ctx->stream),
+               "fused double drop NTT (level A)");
 }
 
 } // namespace
 
 namespace hpi {
-int drop_last(hp_ctx *ctx, const Plan *plan, size_t logn, size_t L, size_t P2, bool bgv, u64 t, const u64 *x,
-              const u64 *addend, size_t add_poly_stride, size_t add_ct_stride, u32 add_mask, u64 *out, Carver &cv) {
+int drop_last(hp_ctx *ctx, const Plan *plan, size_t logn, size_t L, size_t P2, bool bgv, u64 t, const u64 *x, const Addend &add, u64 *out,
+              Carver &cv) {
     const size_t n = (size_t)1 << logn;
-    HpDropConsts dc;
-    make_drop_consts(plan, L, bgv, t, dc);
     u64 *clast = cv.take(P2 * n);
     u64 *rem = cv.take(P2 * (L - 1) * n);
     int rc;
     if ((rc = drop_coeffs(ctx, plan, logn, L, P2, bgv, t, x, clast))) return rc;
-    return drop_apply(ctx, plan, logn, L, P2, 0, L - 1, dc, x, clast, true, addend, add_poly_stride, add_ct_stride, add_mask, out, rem);
+    return drop_apply(ctx, plan, logn, L, P2, 0, L - 1, bgv, t, x, clast, true, add, out, rem);
+}
+
+int move_rows(hp_ctx *ctx, size_t logn, size_t rows, bool conj, size_t step, const u64 *ct, u64 *moved) {
+    const u32 n = (u32)1 << logn;
+    ProfScope ps(ctx, "elem");
+    if (conj) return chk(ctx, hp_launch_reverse(n, (u32)rows, ct, moved, ctx->stream), "involution");
+    const u32 *perm;
+    int rc = get_cycle_perm(ctx, logn, step, &perm);
+    if (rc) return rc;
+    return chk(ctx, hp_launch_gather(perm, n, (u32)rows, ct, moved, ctx->stream), "cycle");
 }
 } // namespace hpi
 
@@ -427,7 +336,7 @@ static int dev_drop_locked(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *m
     const size_t n = (size_t)1 << logn;
     if ((rc = ws_reserve(ctx, drop_ws_words(n, L, 2 * batch) * 8))) return rc;
     Carver cv(ctx->ws);
-    return drop_last(ctx, plan, logn, L, 2 * batch, bgv, t, ct, nullptr, 0, 0, 0, out, cv);
+    return drop_last(ctx, plan, logn, L, 2 * batch, bgv, t, ct, Addend(), out, cv);
 }
 static int dev_drop(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, bool bgv, uint64_t t, size_t batch,
                     const uint64_t *ct, uint64_t *out) {
@@ -464,7 +373,7 @@ static int relin_core(hp_ctx *ctx, const Plan *plan, size_t logn, size_t L, size
     u64 *ext = cv.take(P * 2 * (L + 1) * n);
     int rc = ext_prod(ctx, plan, logn, L, P, quad + 2 * L * n, 3 * L, key, key_L0, ext, cv);
     if (rc) return rc;
-    return drop_last(ctx, plan, logn, L + 1, 2 * P, bgv, inner_t, ext, quad, L, 3 * L, 3, out, cv);
+    return drop_last(ctx, plan, logn, L + 1, 2 * P, bgv, inner_t, ext, Addend(quad, L, 3 * L, 3), out, cv);
 }
 static size_t relin_ws_words(size_t n, size_t L, size_t P) {
     return padded(P * 2 * (L + 1) * n) / 8 + ext_prod_ws_words(n, L, P) + drop_ws_words(n, L + 1, 2 * P);
@@ -545,32 +454,26 @@ static int dev_ckks_automorphism(hp_ctx *ctx, size_t logn, size_t L, size_t key_
     Carver cv(ctx->ws);
     u64 *moved = cv.take(batch * 2 * L * n);
     u64 *ext = cv.take(batch * 2 * (L + 1) * n);
-    {
+    if (many) {
+        // every ciphertext with its own map (and its polynomials possibly anywhere): sources and maps as kernel arguments
         ProfScope ps(ctx, "elem");
-        if (many) {
-            // every ciphertext with its own map (and its polynomials possibly anywhere): sources and maps as kernel arguments
-            for (size_t b0 = 0; b0 < batch && !rc; b0 += HP_GATHER_TABLE_MAX) {
-                const size_t cnt = batch - b0 < HP_GATHER_TABLE_MAX ? batch - b0 : HP_GATHER_TABLE_MAX;
-                HpGatherTable gt;
-                memset(&gt, 0, sizeof(gt));
-                if ((rc = reserve_cycle_perms(ctx, cnt))) break;   // (a miss in a full map cache empties it: not between these)
-                for (size_t b = b0; b < b0 + cnt && !rc; b++) {
-                    for (size_t h = 0; h < 2; h++) gt.src[b - b0][h] = many->polys ? many->polys[2 * b + h] : ct + (b * 2 + h) * L * n;
-                    if (!(many->conj_of && many->conj_of[b])) rc = get_cycle_perm(ctx, logn, many->steps[b], &gt.perm[b - b0]);
-                }
-                if (!rc) rc = chk(ctx, hp_launch_gather_many(gt, (u32)cnt, (u32)n, (u32)L, moved + b0 * 2 * L * n, ctx->stream), "cycle / involution");
+        for (size_t b0 = 0; b0 < batch && !rc; b0 += HP_GATHER_TABLE_MAX) {
+            const size_t cnt = batch - b0 < HP_GATHER_TABLE_MAX ? batch - b0 : HP_GATHER_TABLE_MAX;
+            HpGatherTable gt;
+            memset(&gt, 0, sizeof(gt));
+            if ((rc = reserve_cycle_perms(ctx, cnt))) break;   // (a miss in a full map cache empties it: not between these)
+            for (size_t b = b0; b < b0 + cnt && !rc; b++) {
+                for (size_t h = 0; h < 2; h++) gt.src[b - b0][h] = many->polys ? many->polys[2 * b + h] : ct + (b * 2 + h) * L * n;
+                if (!(many->conj_of && many->conj_of[b])) rc = get_cycle_perm(ctx, logn, many->steps[b], &gt.perm[b - b0]);
             }
-        } else if (conj) {
-            rc = chk(ctx, hp_launch_reverse((u32)n, (u32)(batch * 2 * L), ct, moved, ctx->stream), "involution");
-        } else {
-            const u32 *perm;
-            if ((rc = get_cycle_perm(ctx, logn, step, &perm))) return rc;
-            rc = chk(ctx, hp_launch_gather(perm, (u32)n, (u32)(batch * 2 * L), ct, moved, ctx->stream), "cycle");
+            if (!rc) rc = chk(ctx, hp_launch_gather_many(gt, (u32)cnt, (u32)n, (u32)L, moved + b0 * 2 * L * n, ctx->stream), "cycle / involution");
         }
+    } else {
+        rc = move_rows(ctx, logn, batch * 2 * L, conj, step, ct, moved);
     }
     if (rc) return rc;
     if ((rc = ext_prod(ctx, plan, logn, L, batch, moved + L * n, 2 * L, key, key_L0, ext, cv, many ? many->keys : nullptr))) return rc;
-    return drop_last(ctx, plan, logn, L + 1, 2 * batch, false, 0, ext, moved, L, 2 * L, 1, out, cv);
+    return drop_last(ctx, plan, logn, L + 1, 2 * batch, false, 0, ext, Addend(moved, L, 2 * L, 1), out, cv);
 }
 
 // mult_low_level + relinearize + drop q_last, processed in sub-batches so the working set
@@ -648,12 +551,12 @@ static int dev_mult(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, const uin
             // level A: relinearize's mod-down and the rescale / mod switch in one transform per output limb (drop_two_last_a)
             u64 *ext = cv.take(P * 2 * (L + 1) * n);
             rc = ext_prod(ctx, plan, logn, L, P, quad + 2 * L * n, 3 * L, key, key_L0, ext, cv);
-            if (!rc) rc = drop_two_last_a(ctx, plan, logn, L, 2 * P, bgv, inner_t, t, ext, quad, L, 3 * L, out + b0 * 2 * (L - 1) * n, cv);
+            if (!rc) rc = drop_two_last_a(ctx, plan, logn, L, 2 * P, bgv, inner_t, t, ext, Addend(quad, L, 3 * L, 3), out + b0 * 2 * (L - 1) * n, cv);
             if (rc) break;
             continue;
         }
         if (!rc) rc = relin_core(ctx, plan, logn, L, P, bgv, inner_t, quad, key, key_L0, lin, cv);
-        if (!rc) rc = drop_last(ctx, plan, logn, L, 2 * P, bgv, t, lin, nullptr, 0, 0, 0, out + b0 * 2 * (L - 1) * n, cv);
+        if (!rc) rc = drop_last(ctx, plan, logn, L, 2 * P, bgv, t, lin, Addend(), out + b0 * 2 * (L - 1) * n, cv);
         if (rc) break;
     }
     ctx->stream = user;
@@ -810,8 +713,7 @@ int hp_dev_drop_coeffs(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *modul
 }
 
 static int drop_apply_range(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, uint64_t plain_modulus, size_t P2,
-                            size_t k0, size_t k1, const uint64_t *x, const uint64_t *clast, bool clast_strict, const uint64_t *addend,
-                            size_t add_poly_stride, size_t add_ct_stride, unsigned add_mask, uint64_t *out) {
+                            size_t k0, size_t k1, const uint64_t *x, const uint64_t *clast, bool clast_strict, const Addend &add, uint64_t *out) {
     HP_ENTER(ctx);
     HP_REQUIRE(ctx, moduli, x, clast, out);
     HP_ALIGNED(ctx, x, clast, out);
@@ -826,23 +728,21 @@ static int drop_apply_range(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *
     if ((rc = ws_reserve(ctx, padded(P2 * (k1 - k0) * n)))) return rc;
     Carver cv(ctx->ws);
     u64 *rem = cv.take(P2 * (k1 - k0) * n);
-    HpDropConsts dc;
-    make_drop_consts(plan, L, plain_modulus != 0, plain_modulus, dc);
     // the _strict form follows the context's parity level (canonical residues at level A); the plain form stays at level B
     LevelScope lvl(ctx, clast_strict ? plan : nullptr);
     if (lvl.rc) return lvl.rc;
-    return drop_apply(ctx, plan, logn, L, P2, k0, k1, dc, x, clast, clast_strict, addend, add_poly_stride, add_ct_stride, add_mask, out, rem);
+    return drop_apply(ctx, plan, logn, L, P2, k0, k1, plain_modulus != 0, plain_modulus, x, clast, clast_strict, add, out, rem);
 }
 
 int hp_dev_drop_apply_range(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, uint64_t plain_modulus, size_t P2,
                             size_t k0, size_t k1, const uint64_t *x, const uint64_t *clast, const uint64_t *addend,
                             size_t add_poly_stride, size_t add_ct_stride, unsigned add_mask, uint64_t *out) {
-    return drop_apply_range(ctx, logn, L, moduli, plain_modulus, P2, k0, k1, x, clast, false, addend, add_poly_stride, add_ct_stride, add_mask, out);
+    return drop_apply_range(ctx, logn, L, moduli, plain_modulus, P2, k0, k1, x, clast, false, Addend(addend, add_poly_stride, add_ct_stride, add_mask), out);
 }
 int hp_dev_drop_apply_range_strict(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, uint64_t plain_modulus, size_t P2,
                                    size_t k0, size_t k1, const uint64_t *x, const uint64_t *clast, const uint64_t *addend,
                                    size_t add_poly_stride, size_t add_ct_stride, unsigned add_mask, uint64_t *out) {
-    return drop_apply_range(ctx, logn, L, moduli, plain_modulus, P2, k0, k1, x, clast, true, addend, add_poly_stride, add_ct_stride, add_mask, out);
+    return drop_apply_range(ctx, logn, L, moduli, plain_modulus, P2, k0, k1, x, clast, true, Addend(addend, add_poly_stride, add_ct_stride, add_mask), out);
 }
 
 } // extern "C"

@@ -491,7 +491,7 @@ void hp_ctx_destroy(hp_ctx *ctx) {
             for (auto &kv : sh->plans) { (void)hipFree(kv.second.d_limbs); if (kv.second.d_limbs_a) (void)hipFree(kv.second.d_limbs_a); }
             for (auto &kv : sh->perms) (void)hipFree(kv.second);
             for (auto &kv : sh->crt) (void)hipFree(kv.second);
-            for (auto &kv : sh->hks) (void)hipFree(kv.second);
+            for (auto &kv : sh->hks) (void)hipFree(kv.second.dev);
             if (sh->range_flag) (void)hipFree(sh->range_flag);
         }
         if (ctx->ws) (void)hipFree(ctx->ws);

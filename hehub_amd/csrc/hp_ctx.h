@@ -4,6 +4,7 @@
 //   hp_api_poly.cpp    drop-in host entry points, device-resident polynomial batches, encrypt / decrypt cores, base conversions
 //   hp_api_scheme.cpp  key switch, drop-last-prime, relinearisation, rotations, the mult pipelines, limb-range stages
 //   hp_api_hks.cpp     hybrid key switch (extension)
+//   hp_drop.cpp        the constants of the fused drop launches (hp_drop.h: HpDropArgs field by field); host only, no HIP, no context
 //   hp_node.cpp        several contexts (GPUs) behind one handle: batch slices and the limb-sharded exchange
 // There is NO CPU fallback anywhere: every entry point launches HIP kernels or fails.
 #pragma once
@@ -47,6 +48,13 @@ struct ProfEvent {
 // caches of small device objects are bounded: when one is full it is emptied (after a device synchronise), not grown
 constexpr size_t MAX_PERMS = 1024, MAX_CRT = 128, MAX_HKS = 16;
 
+// hybrid key switch constants of one (extended moduli, (k, alpha)): the device block, and what the host needs of it per call
+struct HksEntry {
+    HpHksConsts *dev = nullptr;
+    HksLimbConsts host;
+};
+typedef std::map<std::pair<std::vector<u64>, std::pair<size_t, size_t>>, HksEntry> HksCache;
+
 } // namespace hpi
 
 namespace hpi {
@@ -62,7 +70,7 @@ struct Shared {
     std::map<std::pair<size_t, std::vector<u64>>, Plan> plans;   // (logn, moduli); logn == 0: no transforms needed
     std::map<std::pair<size_t, size_t>, u32 *> perms;                 // (logn, step mod N/2) -> gather map
     std::map<std::pair<std::vector<u64>, u64>, HpCrtConsts *> crt;    // (old moduli, new modulus) -> CRT-branch constants
-    std::map<std::pair<std::vector<u64>, std::pair<size_t, size_t>>, HpHksConsts *> hks;   // (extended moduli, (k, alpha))
+    HksCache hks;                                                     // (extended moduli, (k, alpha))
     // level A range guard (hp_ntt_a.hip: RangeAcc): one sticky device word for the family.  Every member keeps its OWN "a level-A call
     // of mine has not been checked yet" state (hp_ctx::a_pending) and reads the word after a synchronisation of its OWN stream; a
     // non-zero word is counted here (`range_trips`) and cleared, and every member that had level-A work pending when a trip was
@@ -96,7 +104,7 @@ struct hp_ctx {
     std::map<std::pair<size_t, std::vector<u64>>, hpi::Plan> &plans;
     std::map<std::pair<size_t, size_t>, u32 *> &perms;
     std::map<std::pair<std::vector<u64>, u64>, HpCrtConsts *> &crt;
-    std::map<std::pair<std::vector<u64>, std::pair<size_t, size_t>>, HpHksConsts *> &hks;
+    hpi::HksCache &hks;
     void *ws = nullptr;
     size_t ws_bytes = 0;
     unsigned long ws_generation = 0;   // bumped whenever the workspace is reallocated or released (captured graphs go stale)
@@ -270,7 +278,9 @@ size_t ext_prod_ws_words(size_t n, size_t L, size_t P);
 size_t drop_ws_words(size_t n, size_t L, size_t P2);
 int ks_coef(hp_ctx *ctx, const Plan *plan, size_t logn, size_t L, size_t P, size_t j0, size_t j1, const u64 *pt, size_t pt_pstride,
             u64 *coef, bool for_spread_a = false);
-int drop_last(hp_ctx *ctx, const Plan *plan, size_t logn, size_t L, size_t P2, bool bgv, u64 t, const u64 *x, const u64 *addend,
-              size_t add_poly_stride, size_t add_ct_stride, u32 add_mask, u64 *out, Carver &cv);
+int drop_last(hp_ctx *ctx, const Plan *plan, size_t logn, size_t L, size_t P2, bool bgv, u64 t, const u64 *x, const Addend &add,
+              u64 *out, Carver &cv);
+// moved = the automorphism of ct [rows][n]: the involution (conj), or the cycle by `step`
+int move_rows(hp_ctx *ctx, size_t logn, size_t rows, bool conj, size_t step, const u64 *ct, u64 *moved);
 
 } // namespace hpi

@@ -2,8 +2,7 @@
 // Every launcher enqueues on `stream` and returns the hipError_t of the launch.
 #pragma once
 #include "hp_device.h"
-
-#define HP_MAX_LIMBS 32
+#include "hp_drop.h"   // HP_MAX_LIMBS, HpDropConsts, HpDropArgs, HpInvMixArgs
 
 // ---- transform jobs -----------------------------------------------------------
 // A transform launch processes W independent limb transforms ("work items").
@@ -146,57 +145,17 @@ struct HpKeyTable {
 hipError_t hp_launch_ks_inner_many(const HpLimb *limbs, u32 L, u32 k_first, u32 kc, u32 key_Le, u32 n, u32 P, const u64 *digits,
                                    const u64 *pt, u32 pt_pstride, const HpKeyTable &keys, u64 *out, hipStream_t stream);
 
-// drop-last-prime helpers (rescaling.cpp:46-75 / mod_switch.cpp:45-77)
-struct HpDropConsts {
-    u64 q_last, half_q_last;
-    u64 r[HP_MAX_LIMBS];       // q_last mod q_k
-    u64 inv[HP_MAX_LIMBS];     // q_last^{-1} mod q_k (already reduced mod q_k)
-    u64 inv_h[HP_MAX_LIMBS];
-    int bgv;
-    u64 t[HP_MAX_LIMBS], t_h[HP_MAX_LIMBS];          // plain_modulus mod q_k      (mod_switch.cpp:70)
-    u64 qlt[HP_MAX_LIMBS], qlt_h[HP_MAX_LIMBS];      // (q_last mod t) mod q_k     (mod_switch.cpp:76)
-};
-// Fused form for the tiled transform (rescaling.cpp:54-74 / mod_switch.cpp:52-76 in ONE launch): the forward
-// NTT of the remainder limbs reads the strict last-limb coefficients, applies Barrett + centring (+ *t) while
-// loading, and finishes with out = ((x - NTT(rem)) * inv) [* (q_last mod t)] [+ addend] while storing.
-struct HpDropArgs {
-    HpDropConsts dc;
-    int small_rem;         // 1: q_last <= 2 q_k for every limb of the launch: the remainder of c < q_last is c - [c >= q_k] q_k (the canonical
-                           //    residue either way; saves the Barrett quotient).  Honoured by the compile-time flavours only.
-    int raw_input;         // 1: the transform's input rows already are the per-limb remainders (hybrid key switch): no
-                           //    Barrett / centring prologue
-    u32 out_stride;        // limbs between consecutive polynomials of out (L - 1 for a plain drop)
-    int fin_on;            // 1: one more per-limb multiplication AFTER the addend (hybrid key switch: merged rescale)
-    u64 fin[HP_MAX_LIMBS], fin_h[HP_MAX_LIMBS];
-    const u64 *comb;       // non-NULL (with raw_input): input = src + comb_mul[k] * centre_k(comb[p2]), comb [P2][N] strict modulo 2*comb_half+1
-    u64 comb_half, comb_r[HP_MAX_LIMBS], comb_mul[HP_MAX_LIMBS], comb_mul_h[HP_MAX_LIMBS];
-    u64 q2_last, half_q2_last;   // level A, two drops in one launch (hp_ntt_a.hip: DropPre2A): the second modulus dropped; comb = its
-                                 // strict coefficient rows [P2][N]; per limb (t, t_h) = m_k, (comb_mul, comb_mul_h) = m2_k, (inv, inv_h) = A_k,
-                                 // (qlt, qlt_h) = B_k, all as bit patterns of doubles (v, RN(v / q_k))
-    const u64 *x;          // [P2][L][n]: polynomial p2 at x + p2*L*n, limb k at + k*n
-    u32 L;                 // limbs of x (the last one is being dropped)
-    const u64 *addend;     // optional [.][.][n]: row (p2>>1)*add_ct_stride + (p2&1)*add_poly_stride + k
-    u32 add_poly_stride, add_ct_stride;
-    u32 add_mask;          // bit h set: polynomial h of each ciphertext gets the addend (relinearize 3, rotate 1)
-    u64 *out;              // [P2][L-1][n]
-};
+// drop-last-prime (rescaling.cpp:46-75 / mod_switch.cpp:45-77).  Fused form for the tiled transform (rescaling.cpp:54-74 /
+// mod_switch.cpp:52-76 in ONE launch): the forward NTT of the remainder limbs reads the strict last-limb coefficients, applies
+// Barrett + centring (+ *t) while loading, and finishes with out = ((x - NTT(rem)) * inv) [* (q_last mod t)] [+ addend] while
+// storing.  hp_drop.h has HpDropArgs field by field, at both parity levels.
 // job: HP_NTT_BATCH over L-1 limbs and P2 polynomials with src = clast [P2][n] (src_pstride 1, src_kstride 0)
 hipError_t hp_launch_ntt_fast_drop(const HpNttJob &job, const HpDropArgs &da, hipStream_t stream);
 // the same for a launch of few limbs, split over N / 2048 workgroups per limb (hp_ntt_split.hip); job.dst = scratch rows [P2][kc][n]
 hipError_t hp_launch_ntt_split_drop(const HpNttJob &job, const HpDropArgs &da, hipStream_t stream);
-// level A: dc.q_last / half_q_last and the pairs (inv, inv_h), (t, t_h), (qlt, qlt_h) hold bit patterns of doubles (v, RN(v / q_k));
-// r, small_rem, raw_input, fin, comb are not used; output rows are canonical residues
+// level A (one drop, or two in one transform when da.comb is set); output rows are canonical residues
 hipError_t hp_launch_ntt_a_drop(const HpNttJob &job, const HpDropArgs &da, hipStream_t stream);
-// level A, inverse of ONE limb (job.L == 1) whose input is A * src + add and whose output has K * centre(cprev) subtracted
-// (hp_ntt_a.hip: ntt_inv_a_body MIX); every constant as the bit pattern of a double, (v, RN(v / q)) for the multipliers
-struct HpInvMixArgs {
-    const u64 *add;            // addend rows already at the limb: polynomial p at (p >> 1) * add_ct_stride + (p & 1) * add_poly_stride limbs
-    u32 add_poly_stride, add_ct_stride;
-    u64 A, A_h;
-    const u64 *cprev;          // [P][N] strict coefficients modulo prev_q
-    u64 prev_q, prev_half;
-    u64 K, K_h;
-};
+// level A, inverse of ONE limb (job.L == 1) combined from a row and an addend (HpInvMixArgs, hp_drop.h)
 hipError_t hp_launch_ntt_a_inv_mix(const HpNttJob &job, const HpInvMixArgs &mx, hipStream_t stream);
 
 // clast [P2][n] (strict coefficients of the last limb) -> rem [P2][L-1][n]

@@ -288,3 +288,29 @@ def test_hybrid_key_switch_at_parity_level_a(eng, orc, logn, L, k, alpha):
             continue
         m = np.array(mods, dtype=U)[None, None, :, None]
         assert (b < 2 * m).all() and np.array_equal(a % m, b % m)
+
+
+@pytest.mark.parametrize("knob", ["HP_HKS_COMBINE_KERNEL", "HP_HKS_TWO_STEP"])
+def test_hybrid_mult_at_parity_level_a_with_the_other_compositions(eng, knob, monkeypatch):
+    """The hybrid mult at level A when the ModDown + rescale combination is its own kernel (the merged transform then runs at level B
+    inside a level-A call) and when the rescale is a separate drop: the residues of the default engine's level-B words, every word a
+    lazy word.  N = 2048 is the smallest degree with the fused drop kernels; L = 4, alpha = 2: two digits, a limb range longer than one."""
+    from hehub_amd.engine import Engine
+
+    logn, L, k, alpha, B = 11, 4, 2, 2, 2
+    mext = P.P40[:L] + (P.P50 + P.P40[L:])[:k]
+    n, q = 1 << logn, mext[:L]
+    rng = SplitMix(1700 + logn + L)
+    ct1 = rng.poly((B, 2, L, n), q); ct2 = rng.poly((B, 2, L, n), q)
+    key = rng.poly(((L + alpha - 1) // alpha, 2, L + k, n), mext)
+    a = eng.to_host(eng.ckks_mult_hks(mext, k, alpha, eng.to_device(ct1), eng.to_device(ct2), eng.to_device(key)))
+    monkeypatch.setenv(knob, "1")
+    e = Engine(0)
+    try:
+        e.set_parity_level("A")
+        b = e.to_host(e.ckks_mult_hks(mext, k, alpha, e.to_device(ct1), e.to_device(ct2), e.to_device(key)))
+        e.sync()   # (the range guard stays quiet)
+    finally:
+        e.close()
+    m = np.array(q[:-1], dtype=U)[None, None, :, None]
+    assert (b < 2 * m).all() and np.array_equal(a % m, b % m)
