@@ -16,8 +16,10 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libhehub_amd.so")
-SOURCES = ["hp_ctx.cpp", "hp_prof.cpp", "hp_api_poly.cpp", "hp_api_scheme.cpp", "hp_api_hks.cpp", "hp_node.cpp", "hp_tables.cpp", "hp_drop.cpp", "hp_wire.cpp",
-           "hp_elem.hip", "hp_hks.hip", "hp_ntt_generic.hip", "hp_ntt_split.hip", "hp_ntt_fast.hip", "hp_ntt_a.hip"]
+SOURCES = ["hp_ctx.cpp", "hp_prof.cpp", "hp_api_poly.cpp", "hp_api_scheme.cpp", "hp_api_hks.cpp", "hp_node.cpp", "hp_tables.cpp",
+           "hp_drop.cpp", "hp_wire.cpp",
+           "hp_elem.hip", "hp_ks.hip", "hp_edge.hip", "hp_hks.hip",   # coefficient-wise kernels over hp_elem.h
+           "hp_ntt_generic.hip", "hp_ntt_split.hip", "hp_ntt_fast.hip", "hp_ntt_a.hip"]
 # the FP64 residue kernels rely on separately rounded products (error-free transformations): no contraction of a * b + c
 EXTRA_FLAGS = {"hp_ntt_a.hip": ["-ffp-contract=off"]}
 ARCH = "gfx950"
@@ -48,7 +50,8 @@ def build_lib(force: bool = False, verbose: bool = False) -> str:
         obj = os.path.join(LIBDIR, src.rsplit(".", 1)[0] + ".o")
         objs.append(obj)
         if force or _stale(obj, [spath] + headers):
-            cmd = [hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC"] + EXTRA_FLAGS.get(src, []) + ["-x", "hip", "-c", spath, "-o", obj]
+            cmd = ([hipcc, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC"] + EXTRA_FLAGS.get(src, [])
+                   + ["-x", "hip", "-c", spath, "-o", obj])
             if verbose:
                 print(" ".join(cmd), file=sys.stderr)
             subprocess.run(cmd, check=True)
@@ -75,7 +78,8 @@ def build_host(force: bool = False, verbose: bool = False) -> str:
     build_lib(force=False, verbose=verbose)
     hdir = os.path.join(HERE, "host")
     srcs = [os.path.join(hdir, f) for f in HOST_SOURCES]
-    deps = srcs + [os.path.join(hdir, f) for f in os.listdir(hdir) if f.endswith(".hpp")] + [os.path.join(os.path.dirname(HERE), "include", "hehub_amd.h")]
+    deps = (srcs + [os.path.join(hdir, f) for f in os.listdir(hdir) if f.endswith(".hpp")]
+            + [os.path.join(os.path.dirname(HERE), "include", "hehub_amd.h")])
     if force or _stale(HOST_LIB, deps):
         cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall"] + srcs + ["-o", HOST_LIB, f"-L{LIBDIR}", "-lhehub_amd",
                "-Wl,-rpath,$ORIGIN"]

@@ -131,7 +131,7 @@ static int hks_front(hp_ctx *ctx, const Plan *plan, const HpHksConsts *hc, size_
         ProfScope ps(ctx, "hks_moddown");
         if ((rc = chk(ctx, hp_launch_hks_moddown(plan->d_limbs, hc, (u32)k, (u32)n, (u32)(2 * P), yp, rem, ctx->stream), "hks_moddown")))
             return rc;
-    } else {   // many special primes: one composition per target modulus (hp_elem.hip)
+    } else {   // many special primes: one composition per target modulus (hp_edge.hip)
         const Plan *pplan;
         if ((rc = get_plan(ctx, 0, mext + L, k, false, &pplan))) return rc;
         for (size_t i = 0; i < L; i++) {
