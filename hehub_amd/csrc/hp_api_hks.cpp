@@ -87,14 +87,14 @@ static size_t hks_ws_words(size_t n, size_t L, size_t k, size_t nd, size_t P) {
 
 // key switch of P polynomials pt (NTT form, L limbs, row stride pt_pstride) with a hybrid key u64[nd][2][L+k][N]:
 // out [P][2][L][N] = ModDown( sum_d D_d * key_d ) [+ addend rows (p2>>1)*add_ct_stride + (p2&1)*add_poly_stride + i]
-// first part: ks [P][2][E][N] = sum_d D_d * key_d (NTT form) and rem [2P][L][N] = the centred exact conversion of its P-part into
-// every q_i (coefficient form)
-static int hks_front(hp_ctx *ctx, const Plan *plan, const HpHksConsts *hc, size_t logn, size_t L, size_t k, size_t alpha, size_t P,
-                     const u64 *pt, size_t pt_pstride, const u64 *key, const uint64_t *mext, u64 **ks_out, u64 **rem_out, Carver &cv) {
+// The digit stage: lifted [P][nd][E][N] = every digit's exact integer, in NTT form, in every modulus outside the digit (the slots
+// inside a digit stay unwritten: there D_d is the input limb itself).  All that depends on the input alone -- a rotation that
+// is applied to these rows afterwards (hp_dev_ckks_rotate_hoisted_hks) shares them with every other rotation.
+static int hks_digits(hp_ctx *ctx, const Plan *plan, const HpHksConsts *hc, size_t logn, size_t L, size_t k, size_t alpha, size_t P,
+                      const u64 *pt, size_t pt_pstride, u64 **lifted_out, Carver &cv) {
     const size_t n = (size_t)1 << logn, E = L + k, nd = (L + alpha - 1) / alpha;
-    u64 *coef = cv.take(P * L * n), *lifted = cv.take(P * nd * E * n), *ks = cv.take(P * 2 * E * n);
-    u64 *yp = cv.take(2 * P * k * n), *rem = cv.take(2 * P * L * n);
-    *ks_out = ks; *rem_out = rem;
+    u64 *coef = cv.take(P * L * n), *lifted = cv.take(P * nd * E * n);
+    *lifted_out = lifted;
     int rc;
     // coefficients of the input, strictly reduced (as rgsw.cpp:103-105)
     if ((rc = ks_coef(ctx, plan, logn, L, P, 0, L, pt, pt_pstride, coef))) return rc;
@@ -103,23 +103,24 @@ static int hks_front(hp_ctx *ctx, const Plan *plan, const HpHksConsts *hc, size_
         if ((rc = chk(ctx, hp_launch_hks_modup(plan->d_limbs, hc, (u32)alpha, (u32)nd, (u32)n, (u32)P, coef, lifted, ctx->stream), "hks_modup")))
             return rc;
     }
-    {   // transforms of the lifted limbs, in place
-        HpNttJob j;
-        memset(&j, 0, sizeof(j));
-        j.limbs = plan->d_limbs; j.src = lifted; j.dst = lifted; j.logn = (u32)logn; j.L = (u32)L; j.P = (u32)P;
-        j.hks_nd = (u32)nd; j.hks_E = (u32)E; j.hks_alpha = (u32)alpha; j.mode = HP_NTT_HKS;
-        j.W = (u32)(L * (nd - 1) * P + k * nd * P);
-        // parity level A: the lifted rows are canonical residues (ModUp's exact conversion), the inner product takes any
-        // representative, and hybrid results have no word-level contract with hehub (other keys): the FP64 transform where allowed
-        if (ctx->cur_a) j.limbs_a = plan->d_limbs_a;
-        if ((rc = run_ntt(ctx, j))) return rc;
-    }
-    {
-        ProfScope ps(ctx, "ks_inner");
-        if ((rc = chk(ctx, hp_launch_hks_inner(plan->d_limbs, (u32)L, (u32)E, (u32)nd, (u32)alpha, (u32)n, (u32)P, lifted, pt, (u32)pt_pstride,
-                                               key, ks, ctx->stream), "hks_inner")))
-            return rc;
-    }
+    // transforms of the lifted limbs, in place
+    HpNttJob j;
+    memset(&j, 0, sizeof(j));
+    j.limbs = plan->d_limbs; j.src = lifted; j.dst = lifted; j.logn = (u32)logn; j.L = (u32)L; j.P = (u32)P;
+    j.hks_nd = (u32)nd; j.hks_E = (u32)E; j.hks_alpha = (u32)alpha; j.mode = HP_NTT_HKS;
+    j.W = (u32)(L * (nd - 1) * P + k * nd * P);
+    // parity level A: the lifted rows are canonical residues (ModUp's exact conversion), the inner product takes any
+    // representative, and hybrid results have no word-level contract with hehub (other keys): the FP64 transform where allowed
+    if (ctx->cur_a) j.limbs_a = plan->d_limbs_a;
+    return run_ntt(ctx, j);
+}
+
+// The rest, after the inner product ks [P][2][E][N] = sum_d D_d * key_d (NTT form): rem [2P][L][N] = the centred exact conversion
+// of its P-part into every q_i (coefficient form); yp [2P][k][N] is scratch
+static int hks_pdown(hp_ctx *ctx, const Plan *plan, const HpHksConsts *hc, size_t logn, size_t L, size_t k, size_t P, const u64 *ks,
+                     const uint64_t *mext, u64 *yp, u64 *rem) {
+    const size_t n = (size_t)1 << logn, E = L + k;
+    int rc;
     // ModDown: coefficients of the P-part (strict), centred exact conversion into every q_i, transform, subtract, * P^-1
     {
         HpNttJob j = batch_job(plan, logn, k, 2 * P, ks + L * n, yp, E, k, 1, 1);
@@ -146,6 +147,24 @@ static int hks_front(hp_ctx *ctx, const Plan *plan, const HpHksConsts *hc, size_
     return HP_OK;
 }
 
+// the two halves around the plain inner product: ks [P][2][E][N] and rem [2P][L][N] of one key
+static int hks_front(hp_ctx *ctx, const Plan *plan, const HpHksConsts *hc, size_t logn, size_t L, size_t k, size_t alpha, size_t P,
+                     const u64 *pt, size_t pt_pstride, const u64 *key, const uint64_t *mext, u64 **ks_out, u64 **rem_out, Carver &cv) {
+    const size_t n = (size_t)1 << logn, E = L + k, nd = (L + alpha - 1) / alpha;
+    u64 *lifted;
+    int rc;
+    if ((rc = hks_digits(ctx, plan, hc, logn, L, k, alpha, P, pt, pt_pstride, &lifted, cv))) return rc;
+    u64 *ks = cv.take(P * 2 * E * n), *yp = cv.take(2 * P * k * n), *rem = cv.take(2 * P * L * n);
+    *ks_out = ks; *rem_out = rem;
+    {
+        ProfScope ps(ctx, "ks_inner");
+        if ((rc = chk(ctx, hp_launch_hks_inner(plan->d_limbs, (u32)L, (u32)E, (u32)nd, (u32)alpha, (u32)n, (u32)P, lifted, pt, (u32)pt_pstride,
+                                               key, ks, ctx->stream), "hks_inner")))
+            return rc;
+    }
+    return hks_pdown(ctx, plan, hc, logn, L, k, P, ks, mext, yp, rem);
+}
+
 // Parity level A for the drops that end a hybrid key switch (round 6; DESIGN section 7 item 1 of round 5): the FP64 drop kernels of
 // hp_ntt_a.hip take them as they are -- their compile-time flavours 1 / 2 / 5 (no addend / addend on both polynomials / on polynomial 0)
 // for ModDown, flavour 6 (two drops in one transform) for ModDown merged with the rescale.  What differs from hehub's drops is only
@@ -166,12 +185,11 @@ static int hks_down_fused(hp_ctx *ctx, const Plan *plan, const HksEntry *he, siz
     return chk(ctx, hp_launch_ntt_a_drop(fj, da, ctx->stream), what_a);
 }
 
-static int hks_switch(hp_ctx *ctx, const Plan *plan, const HksEntry *he, size_t logn, size_t L, size_t k, size_t alpha, size_t P,
-                      const u64 *pt, size_t pt_pstride, const u64 *key, const Addend &add, const uint64_t *mext, u64 *out, Carver &cv) {
+// the end of a switch: out [P][2][L][N] = (ks - NTT(rem)) * P^-1 [+ addend]
+static int hks_down(hp_ctx *ctx, const Plan *plan, const HksEntry *he, size_t logn, size_t L, size_t k, size_t P, const u64 *ks, u64 *rem,
+                    const Addend &add, const uint64_t *mext, u64 *out) {
     const size_t n = (size_t)1 << logn, E = L + k;
-    u64 *ks, *rem;
     int rc;
-    if ((rc = hks_front(ctx, plan, he->dev, logn, L, k, alpha, P, pt, pt_pstride, key, mext, &ks, &rem, cv))) return rc;
     if (fused_drop_ok(ctx, logn)) {
         HpDropArgs da = drop_args(ks, E, add, out, L);
         return hks_down_fused(ctx, plan, he, logn, L, 0, L, 2 * P, rem, da, ctx->cur_a && a_drop_shape(add), mext, "hks fused ModDown",
@@ -181,6 +199,14 @@ static int hks_switch(hp_ctx *ctx, const Plan *plan, const HksEntry *he, size_t 
     ProfScope ps(ctx, "hks_down_fin");
     return chk(ctx, hp_launch_hks_down_fin(plan->d_limbs, he->dev, (u32)L, (u32)n, (u32)(2 * P), ks, rem, add.rows, add.poly_stride,
                                            add.ct_stride, add.mask, out, ctx->stream), "hks_down_fin");
+}
+
+static int hks_switch(hp_ctx *ctx, const Plan *plan, const HksEntry *he, size_t logn, size_t L, size_t k, size_t alpha, size_t P,
+                      const u64 *pt, size_t pt_pstride, const u64 *key, const Addend &add, const uint64_t *mext, u64 *out, Carver &cv) {
+    u64 *ks, *rem;
+    int rc;
+    if ((rc = hks_front(ctx, plan, he->dev, logn, L, k, alpha, P, pt, pt_pstride, key, mext, &ks, &rem, cv))) return rc;
+    return hks_down(ctx, plan, he, logn, L, k, P, ks, rem, add, mext, out);
 }
 
 static int hks_args_ok(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, size_t batch) {
@@ -240,6 +266,91 @@ extern "C" int hp_dev_ckks_rotate_hks(hp_ctx *ctx, size_t logn, size_t L, size_t
 extern "C" int hp_dev_ckks_conjugate_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t batch,
                               const uint64_t *ct, const uint64_t *conj_key, uint64_t *out) {
     return dev_hks_automorphism(ctx, logn, L, k, alpha, moduli_ext, batch, true, 0, ct, conj_key, out);
+}
+
+// Hoisted rotations: `rotations` automorphisms of every ciphertext, each with its own key, over ONE digit stage.  The digit rows are
+// those of the unrotated c1; rotation r reads them through its map inside the inner product (k_hks_inner_hoisted).  Moving a
+// transformed digit row is the transform of the moved digit read as a SIGNED integer -- the automorphism negates some coefficients,
+// and -x stays -x in every modulus instead of becoming q_j - x inside the digit and being lifted from there -- so the lifted limbs
+// hold another representative than hp_dev_ckks_rotate_hks's, of the same magnitude bound |x| < Q_d: different words, the same
+// decryption.  Everything after the inner product runs as for any switch, on the polynomials (b, r) -> b * rotations + r.
+// The rotations are processed HOIST_POLYS / batch at a time (at least one, at most one argument table) against the same digit
+// rows: the working set of a pass is that of an unhoisted rotation of HOIST_POLYS ciphertexts, whatever `rotations` is.
+constexpr size_t HOIST_POLYS = 32;
+extern "C" int hp_dev_ckks_rotate_hoisted_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                              size_t batch, size_t rotations, const size_t *steps, const unsigned char *conj,
+                                              const uint64_t *ct, const uint64_t *const *keys, uint64_t *out) {
+    HP_ENTER(ctx);
+    HP_REQUIRE(ctx, moduli_ext, steps, ct, keys, out);
+    HP_ALIGNED(ctx, ct, out);
+    int rc = hks_args_ok(ctx, logn, L, k, alpha, batch);
+    if (rc) return rc;
+    if (rotations == 0) return fail(ctx, HP_EINVAL, "rotate_hoisted: no rotations");
+    for (size_t r = 0; r < rotations; r++) {
+        if (!keys[r] || ((uintptr_t)keys[r] & 15u)) return fail(ctx, HP_EINVAL, "rotate_hoisted: NULL or misaligned key");
+        if (!(conj && conj[r]) && steps[r] >= ((size_t)1 << 17)) return fail(ctx, HP_EINVAL, "rotation step out of range");
+    }
+    const size_t n = (size_t)1 << logn, E = L + k, nd = (L + alpha - 1) / alpha;
+    {   // the output is written while later rotations still read the input
+        const uintptr_t c0 = (uintptr_t)ct, c1 = c0 + batch * 2 * L * n * 8, o0 = (uintptr_t)out, o1 = o0 + batch * rotations * 2 * L * n * 8;
+        if (o0 < c1 && c0 < o1) return fail(ctx, HP_EINVAL, "rotate_hoisted: the output overlaps the input");
+    }
+    const Plan *plan;
+    if ((rc = get_plan(ctx, logn, moduli_ext, E, true, &plan))) return rc;
+    const HksEntry *he;
+    if ((rc = get_hks_consts(ctx, moduli_ext, L, k, alpha, &he))) return rc;
+    LevelScope lvl(ctx, plan);   // level A: the digit stage and the drops on the FP64 kernels, as in hp_dev_hks_switch
+    if (lvl.rc) return lvl.rc;
+    size_t pass = std::max<size_t>(1, HOIST_POLYS / batch);   // rotations per pass
+    pass = std::min(std::min(pass, rotations), (size_t)HP_HOIST_TABLE_MAX);
+    const size_t PP = batch * pass;                            // switched polynomials per pass
+    const size_t words = padded(batch * L * n) / 8 + padded(batch * nd * E * n) / 8 + padded(PP * L * n) / 8 + padded(PP * 2 * E * n) / 8 +
+                         padded(2 * PP * k * n) / 8 + padded(2 * PP * L * n) / 8;
+    if ((rc = ws_reserve(ctx, words * 8))) return rc;
+    Carver cv(ctx->ws);
+    u64 *lifted;
+    if ((rc = hks_digits(ctx, plan, he->dev, logn, L, k, alpha, batch, ct + L * n, 2 * L, &lifted, cv))) return rc;
+    u64 *moved0 = cv.take(PP * L * n), *ks = cv.take(PP * 2 * E * n), *yp = cv.take(2 * PP * k * n), *rem = cv.take(2 * PP * L * n);
+    for (size_t r0 = 0; r0 < rotations; r0 += pass) {
+        const size_t cnt = std::min(pass, rotations - r0), P = batch * cnt;   // this pass: polynomial b * cnt + r
+        HpHoistTable ht;
+        memset(&ht, 0, sizeof(ht));
+        if ((rc = reserve_cycle_perms(ctx, cnt))) return rc;   // (a miss in a full map cache empties it: not between these)
+        for (size_t r = 0; r < cnt; r++) {
+            ht.key[r] = keys[r0 + r];
+            if (!(conj && conj[r0 + r]) && (rc = get_cycle_perm(ctx, logn, steps[r0 + r], &ht.map[r]))) return rc;
+        }
+        {   // the moved c0 of every (b, r), for the addend
+            ProfScope ps(ctx, "elem");
+            for (size_t e0 = 0; e0 < P; e0 += HP_GATHER_TABLE_MAX) {
+                const size_t ec = std::min<size_t>(HP_GATHER_TABLE_MAX, P - e0);
+                HpGatherTable gt;
+                memset(&gt, 0, sizeof(gt));
+                for (size_t e = e0; e < e0 + ec; e++) {
+                    gt.src[e - e0][0] = ct + (e / cnt) * 2 * L * n;
+                    gt.perm[e - e0] = ht.map[e % cnt];
+                }
+                if ((rc = chk(ctx, hp_launch_gather_many(gt, (u32)ec, (u32)n, (u32)L, moved0 + e0 * L * n, ctx->stream, 1), "cycle / involution")))
+                    return rc;
+            }
+        }
+        {
+            ProfScope ps(ctx, "ks_inner");
+            if ((rc = chk(ctx, hp_launch_hks_inner_hoisted(plan->d_limbs, (u32)L, (u32)E, (u32)nd, (u32)alpha, (u32)n, (u32)batch, (u32)cnt,
+                                                           lifted, ct + L * n, (u32)(2 * L), ht, ks, ctx->stream), "hks_inner_hoisted")))
+                return rc;
+        }
+        if ((rc = hks_pdown(ctx, plan, he->dev, logn, L, k, P, ks, moduli_ext, yp, rem))) return rc;
+        // out[b][r0 + r]: one launch when the pass holds every rotation, else one per ciphertext (its rotations are adjacent in out)
+        const size_t launches = cnt == rotations ? 1 : batch, per = P / launches;
+        for (size_t b = 0; b < launches; b++) {
+            const Addend add(moved0 + b * per * L * n, L, L, 1);
+            if ((rc = hks_down(ctx, plan, he, logn, L, k, per, ks + b * per * 2 * E * n, rem + b * per * 2 * L * n, add, moduli_ext,
+                               out + (b * rotations + r0) * 2 * L * n)))
+                return rc;
+        }
+    }
+    return HP_OK;
 }
 
 // ckks::mult_low_level + relinearisation with a hybrid key + rescale by the last ciphertext modulus

@@ -44,6 +44,11 @@ struct ElemTile {
     u32 row, chunk;   // blockIdx.x = row * chunks + chunk
     u32 n, cw;        // words per row, words per chunk
     HP_DEV ElemTile(u32 n, u32 chunks, u32 cw = ELEM_CHUNK) : row(blockIdx.x / chunks), chunk(blockIdx.x % chunks), n(n), cw(cw) {}
+    // a kernel that numbers its workgroups itself (k_hks_inner_hoisted: by XCD) names the tile
+    struct At {
+        u32 row, chunk;
+    };
+    HP_DEV ElemTile(At at, u32 n, u32 cw = ELEM_CHUNK) : row(at.row), chunk(at.chunk), n(n), cw(cw) {}
     HP_DEV u32 begin() const { return chunk * cw; }   // the chunk is the words [begin, end) of the row
     HP_DEV u32 end() const { return min(n, (chunk + 1) * cw); }
     HP_DEV bool full() const { return (chunk + 1) * cw <= n; }   // wholly inside the row (every chunk of the tiled ring degrees)

@@ -259,10 +259,12 @@ hipError_t hp_launch_reverse(u32 n, u32 rows, const u64 *in, u64 *out, hipStream
 }
 
 // cycle / involution of several ciphertexts in one launch, each with its own map and its two polynomials anywhere in device
-// memory (hp_dev_ckks_rotate_many: the sources and maps travel as kernel arguments): out u64[count][2][L][N]
-__global__ void __launch_bounds__(ELEM_THREADS) k_gather_many(HpGatherTable tab, u32 n, u32 chunks, u32 L, u64 *__restrict__ out) {
+// memory (hp_dev_ckks_rotate_many: the sources and maps travel as kernel arguments): out u64[count][polys][L][N], polys = 2, or 1
+// for polynomial 0 alone (hp_dev_ckks_rotate_hoisted_hks moves only c0)
+__global__ void __launch_bounds__(ELEM_THREADS) k_gather_many(HpGatherTable tab, u32 n, u32 chunks, u32 L, u32 polys,
+                                                             u64 *__restrict__ out) {
     const ElemTile tile(n, chunks);
-    const u32 b = tile.row / (2 * L), r = tile.row % (2 * L), h = r / L, k = r % L;
+    const u32 b = tile.row / (polys * L), r = tile.row % (polys * L), h = r / L, k = r % L;
     const u64 *__restrict__ in = tab.src[b][h] + (size_t)k * n;
     const u32 *__restrict__ perm = tab.perm[b];
     u64 *__restrict__ o = out + (size_t)tile.row * n;
@@ -287,10 +289,10 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_gather_many(HpGatherTable tab,
     for (const u32 i : words) __builtin_nontemporal_store(in[perm[i]], o + i);
 }
 
-hipError_t hp_launch_gather_many(const HpGatherTable &tab, u32 count, u32 n, u32 L, u64 *out, hipStream_t stream) {
+hipError_t hp_launch_gather_many(const HpGatherTable &tab, u32 count, u32 n, u32 L, u64 *out, hipStream_t stream, u32 polys) {
     if (count == 0) return hipSuccess;
-    if (count > HP_GATHER_TABLE_MAX) return hipErrorInvalidValue;
-    return elem_launch(k_gather_many, count * 2 * L, n, stream, tab, n, ElemChunks{}, L, out);
+    if (count > HP_GATHER_TABLE_MAX || polys < 1 || polys > 2) return hipErrorInvalidValue;
+    return elem_launch(k_gather_many, count * polys * L, n, stream, tab, n, ElemChunks{}, L, polys, out);
 }
 
 // ---- single-vector kernels (drop-in mod_arith entry points) --------------------------

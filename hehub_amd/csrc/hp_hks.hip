@@ -120,6 +120,93 @@ hipError_t hp_launch_hks_inner(const HpLimb *limbs, u32 L, u32 E, u32 nd, u32 al
                        ElemChunks{}, lifted, pt, pt_pstride, key, out);
 }
 
+// Hoisted rotations (hp_dev_ckks_rotate_hoisted_hks): the digit rows of the UNROTATED c1 are built once and every rotation r reads
+// them through its own map -- k_hks_inner with the digit operand gathered:
+//   out[b][r][half][m][i] = montgomery_128( sum_d D[b][d][m][map_r(i)] * key_r[d][half][m][i] )
+// (the same accumulation order and tail as k_hks_inner: the words follow the model).  Keys and maps are kernel arguments.
+// Key words are read once per launch: streamed, non-temporal.  The digit rows -- nd rows of 8N bytes per (b, m) -- are read again
+// by every rotation, scattered over the whole row: ordinary cached loads, and a numbering of the workgroups that keeps the rows
+// in ONE XCD's L2 while they are needed.  A unit = one modulus m and one group of PT ciphertexts, R * chunks workgroups.
+// Workgroups are dealt round-robin over the 8 XCDs, so of eight consecutive ids each goes to its own unit: an XCD works through
+// all rotations and chunks of one unit (at N = 32768: 1 MiB of digit rows per ciphertext, 4 MiB of L2) before it takes the next.
+// The units that do not fill a group of eight are numbered plainly -- their rows get fetched by every XCD (from the Infinity
+// Cache after the first) -- so that no XCD idles.  A speed matter only: any placement computes the same words.
+template <int PT>
+__global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner_hoisted(const HpLimb *__restrict__ limbs, u32 L, u32 E, u32 nd, u32 alpha,
+                                                                  u32 P, u32 R, u32 n, u32 chunks, const u64 *__restrict__ lifted,
+                                                                  const u64 *__restrict__ pt, u32 pt_pstride, HpHoistTable tab,
+                                                                  u64 *__restrict__ out) {
+    const u32 PG = (P + PT - 1) / PT, units = E * PG, W = R * chunks, grouped = (units & ~7u) * W;
+    u32 unit, w;
+    if (blockIdx.x < grouped) {
+        unit = (blockIdx.x / (8 * W)) * 8 + (blockIdx.x & 7u);
+        w = (blockIdx.x >> 3) % W;
+    } else {
+        unit = (units & ~7u) + (blockIdx.x - grouped) / W;
+        w = (blockIdx.x - grouped) % W;
+    }
+    const u32 m = unit / PG, p0 = (unit % PG) * PT, r = w / chunks;
+    const ElemTile tile(ElemTile::At{unit, w % chunks}, n);
+    const u64 q = limbs[m].q, mqinv = limbs[m].mqinv;
+    const u32 own = (m < L) ? m / alpha : nd;   // the digit this modulus belongs to (none for the special primes)
+    const u64 *__restrict__ key = tab.key[r];
+    const u32 *__restrict__ map = tab.map[r];   // NULL: the involution i -> n - 1 - i
+    for (const u32 i : tile.pairs()) {
+        // where the two digit words come from: the map's pair, or (involution) the 16 bytes at n - 2 - i, swapped
+        uint2 j{n - 2 - i, 0};
+        if (map) j = *reinterpret_cast<const uint2 *>(map + i);
+        HpAcc acc[PT][2][2];   // carry-save columns (hp_device.h)
+#pragma unroll
+        for (int c = 0; c < PT; c++)
+#pragma unroll
+            for (int h = 0; h < 2; h++) { hp_acc_zero(acc[c][h][0]); hp_acc_zero(acc[c][h][1]); }
+        for (u32 d = 0; d < nd; d++) {
+            const U2 g0 = ld_nt(key + (((size_t)d * 2 + 0) * E + m) * n + i);
+            const U2 g1 = ld_nt(key + (((size_t)d * 2 + 1) * E + m) * n + i);
+            const u64 kw[2][2] = {{g0.x, g0.y}, {g1.x, g1.y}};
+#pragma unroll
+            for (int c = 0; c < PT; c++) {
+                const u32 p = min(p0 + c, P - 1);
+                const u64 *src = (d == own) ? pt + ((size_t)p * pt_pstride + m) * n : lifted + (((size_t)p * nd + d) * E + m) * n;
+                U2 t;
+                if (map) {
+                    t.x = src[j.x];
+                    t.y = src[j.y];
+                } else {
+                    const U2 v = *reinterpret_cast<const U2 *>(src + j.x);
+                    t.x = v.y;
+                    t.y = v.x;
+                }
+#pragma unroll
+                for (int h = 0; h < 2; h++) hp_mac2(acc[c][h][0], t.x, kw[h][0], acc[c][h][1], t.y, kw[h][1]);
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < PT; c++) {
+            const u32 p = p0 + c;
+            if (p < P) {
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    const U2 v = acc2_montgomery(acc[c][h][0], acc[c][h][1], q, mqinv);
+                    st_nt(out + ((((size_t)p * R + r) * 2 + h) * E + m) * n + i, v);
+                }
+            }
+        }
+    }
+}
+
+hipError_t hp_launch_hks_inner_hoisted(const HpLimb *limbs, u32 L, u32 E, u32 nd, u32 alpha, u32 n, u32 P, u32 R, const u64 *lifted,
+                                       const u64 *pt, u32 pt_pstride, const HpHoistTable &tab, u64 *out, hipStream_t stream) {
+    if (P == 0 || R == 0) return hipSuccess;
+    if (R > HP_HOIST_TABLE_MAX) return hipErrorInvalidValue;
+    // two ciphertexts per thread share the key words and the map's pair, as in k_hks_inner
+    const u32 PT = P >= 2 ? 2 : 1, chunks = (n + ELEM_CHUNK - 1) / ELEM_CHUNK;
+    const auto k = PT == 2 ? k_hks_inner_hoisted<2> : k_hks_inner_hoisted<1>;
+    k<<<dim3(((P + PT - 1) / PT) * E * R * chunks, 1, 1), ELEM_THREADS, 0, stream>>>(limbs, L, E, nd, alpha, P, R, n, chunks, lifted, pt,
+                                                                                 pt_pstride, tab, out);
+    return hipGetLastError();
+}
+
 // ModDown conversion: Garner digits of the special-prime part once per coefficient, then its exact centred value
 // (x below floor(P/2), x - P from there on; an exact multiple of q_i above the half comes out as q_i, a representative
 // of 0) in every ciphertext modulus

@@ -85,13 +85,13 @@ hipError_t hp_launch_host_rows(bool to_host, const HpHostRows &rows, u32 count, 
 hipError_t hp_launch_gather(const u32 *perm, u32 n, u32 rows, const u64 *in, u64 *out, hipStream_t stream);
 hipError_t hp_launch_reverse(u32 n, u32 rows, const u64 *in, u64 *out, hipStream_t stream);
 // several ciphertexts moved in one launch: ciphertext b = polynomials src[b][0], src[b][1] (u64[L][N] each, anywhere), map perm[b]
-// (NULL: involution) -> out u64[count][2][L][N]
+// (NULL: involution) -> out u64[count][polys][L][N]; polys = 1: polynomial 0 alone
 #define HP_GATHER_TABLE_MAX 32
 struct HpGatherTable {
     const u64 *src[HP_GATHER_TABLE_MAX][2];
     const u32 *perm[HP_GATHER_TABLE_MAX];
 };
-hipError_t hp_launch_gather_many(const HpGatherTable &tab, u32 count, u32 n, u32 L, u64 *out, hipStream_t stream);
+hipError_t hp_launch_gather_many(const HpGatherTable &tab, u32 count, u32 n, u32 L, u64 *out, hipStream_t stream, u32 polys = 2);
 
 // single-vector kernels behind the drop-in mod_arith entry points
 enum HpVecOp : int {
@@ -220,6 +220,16 @@ hipError_t hp_launch_hks_modup(const HpLimb *limbs, const HpHksConsts *hc, u32 a
                                u64 *lifted, hipStream_t stream);
 hipError_t hp_launch_hks_inner(const HpLimb *limbs, u32 L, u32 E, u32 nd, u32 alpha, u32 n, u32 P, const u64 *lifted, const u64 *pt,
                                u32 pt_pstride, const u64 *key, u64 *out, hipStream_t stream);
+// hoisted rotations: the inner product of R rotations over ONE set of digit rows (of the unrotated polynomials), rotation r reading
+// them through map[r] (a cycle map of the context's cache; NULL: the involution) and multiplying by key[r]
+//   -> out [P][R][2][E][n]; keys and maps as kernel arguments
+#define HP_HOIST_TABLE_MAX 32
+struct HpHoistTable {
+    const u64 *key[HP_HOIST_TABLE_MAX];
+    const u32 *map[HP_HOIST_TABLE_MAX];
+};
+hipError_t hp_launch_hks_inner_hoisted(const HpLimb *limbs, u32 L, u32 E, u32 nd, u32 alpha, u32 n, u32 P, u32 R, const u64 *lifted,
+                                       const u64 *pt, u32 pt_pstride, const HpHoistTable &tab, u64 *out, hipStream_t stream);
 // merged ModDown + rescale (hp_engine.cpp: hks_mult): rem[p2][i] += (P mod q_i) * centre(c_last[p2]) for i < L-1, in the
 // coefficient domain; c_last = strict coefficients modulo q_{L-1} of the relinearised limb L-1
 hipError_t hp_launch_hks_combine(const HpLimb *limbs, const HpHksConsts *hc, u32 L, u32 n, u32 P2, const u64 *clast, u64 *rem,

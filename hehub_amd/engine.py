@@ -447,6 +447,20 @@ class Engine:
                                                      self._ptr(ct), self._ptr(key), self._ptr(out)))
         return out
 
+    def ckks_rotate_hoisted_hks(self, moduli_ext, k: int, alpha: int, ct, keys, steps, conj=None):
+        """every ciphertext of ct [B][2][L][n] rotated by steps[r] (conjugated where conj[r]) under ITS hybrid key keys[r] (device
+        tensors), all rotations sharing one digit decomposition of c1 -> [B][R][2][L][n]."""
+        B, _, L, n = ct.shape
+        R = len(keys)
+        assert len(steps) == R and (conj is None or len(conj) == R)
+        out = self.empty((B, R, 2, L, n))
+        kp = (capi.P * R)(*[key.data_ptr() for key in keys])
+        st = (C.c_size_t * R)(*[int(s) for s in steps])
+        cj = (C.c_ubyte * R)(*[1 if c else 0 for c in conj]) if conj is not None else None
+        self._chk(self.lib.hp_dev_ckks_rotate_hoisted_hks(self.h, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), B, R, st, cj,
+                                                          self._ptr(ct), kp, self._ptr(out)))
+        return out
+
     def ckks_mult_hks(self, moduli_ext, k: int, alpha: int, ct1, ct2, key, out=None):
         B, _, L, n = ct1.shape
         out = self.empty((B, 2, L - 1, n)) if out is None else out

@@ -496,6 +496,22 @@ int hp_dev_ckks_rotate_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t 
                            size_t batch, size_t step, const uint64_t *d_ct, const uint64_t *d_rot_key, uint64_t *d_out);
 int hp_dev_ckks_conjugate_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
                               size_t batch, const uint64_t *d_ct, const uint64_t *d_conj_key, uint64_t *d_out);
+/* Hoisted rotations: every ciphertext of d_ct u64[batch][2][L][N] rotated by steps[r] (conjugated where conj[r] != 0; conj may
+ * be NULL, a conjugation ignores its step) and switched with the hybrid key d_keys[r] -- a HOST array of `rotations` device
+ * addresses, each key u64[dnum][2][L+k][N] as for hp_dev_hks_switch -- into d_out u64[batch][rotations][2][L][N].  The digits
+ * of c1 (L inverse transforms, ModUp, L*(dnum-1) + k*dnum forward transforms) are computed ONCE per ciphertext; every rotation
+ * reads the transformed digit rows through its own index map inside the inner product and then pays only ModDown:
+ * 2k inverse + 2L forward transforms per rotation instead of L + L*(dnum-1) + k*dnum + 2k + 2L (L = 10, k = 4, alpha = 3:
+ * 28 instead of 84, plus 56 once per call).
+ * Moving a transformed digit row is the transform of the moved digit read as a SIGNED integer (the automorphism's negated
+ * coefficients stay -x in every modulus), where hp_dev_ckks_rotate_hks lifts the non-negative residues of the moved polynomial:
+ * on the lifted limbs the words DIFFER from hp_dev_ckks_rotate_hks's (step 0 excepted).  Both representatives are bounded by the
+ * digit's modulus product, so the noise bound is the same and both results decrypt alike.
+ * HP_EINVAL before anything is enqueued: the limits of hp_dev_hks_switch, rotations == 0, a step >= 2^17 (not a conjugation), a
+ * NULL or misaligned key address, d_out overlapping d_ct. */
+int hp_dev_ckks_rotate_hoisted_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                   size_t batch, size_t rotations, const size_t *steps, const unsigned char *conj,
+                                   const uint64_t *d_ct, const uint64_t *const *d_keys, uint64_t *d_out);
 /* ckks::mult_low_level + relinearisation with a hybrid key + rescale by q_{L-1}: out u64[batch][2][L-1][N].
  * For N = 2^11 .. 2^15 ModDown and the rescale share one transform per limb: the residues of hp_dev_hks_switch followed by
  * hp_dev_ckks_rescale, in a lazy representative (< 2q) of their own; HP_HKS_TWO_STEP=1 in the environment at hp_ctx_create
