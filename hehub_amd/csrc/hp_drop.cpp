@@ -6,6 +6,29 @@
 
 #include <cstring>
 
+int hp_drop_flavour_b(const HpDropArgs &da, bool *small) {
+    int flav = 0;
+    if (!da.fin_on && !da.raw_input && !da.comb) {
+        if (!da.addend || da.add_mask == 0) flav = 1;
+        else if (da.add_mask == 3u) flav = 2;
+        else if (da.add_mask == 1u && !da.dc.bgv) flav = 5;   // rotation / conjugation: += moved[0]
+        if (flav && flav != 5 && da.dc.bgv) flav += 2;
+    }
+    *small = flav != 0 && da.small_rem != 0;
+    return flav;
+}
+
+int hp_drop_flavour_a(const HpDropArgs &da) {
+    if (da.fin_on || da.raw_input) return -1;
+    int flav = 0;
+    if (da.comb) flav = (da.addend && da.add_mask == 3u) ? (da.dc.bgv ? 7 : 6) : 0;   // two drops at once
+    else if (!da.addend || da.add_mask == 0) flav = 1;
+    else if (da.add_mask == 3u) flav = 2;
+    else if (da.add_mask == 1u && !da.dc.bgv) flav = 5;
+    if (flav && flav < 5 && da.dc.bgv) flav += 2;
+    return flav ? flav : -1;
+}
+
 namespace hpi {
 
 namespace {

@@ -91,6 +91,13 @@ static_assert(offsetof(HpDropArgs, addend) == 3160 && offsetof(HpDropArgs, add_m
 static_assert(offsetof(HpInvMixArgs, add_poly_stride) == 8 && offsetof(HpInvMixArgs, A) == 16 && offsetof(HpInvMixArgs, cprev) == 32, "HpInvMixArgs moved");
 static_assert(offsetof(HpInvMixArgs, prev_q) == 40 && offsetof(HpInvMixArgs, K) == 56 && offsetof(HpInvMixArgs, K_h) == 64, "HpInvMixArgs moved");
 
+// Which compiled flavour of the fused drop kernels a launch takes (the FLAV template argument; hp_ntt_fast.hip and hp_ntt_a.hip
+// have the list).  Level B: 0 (every option read at run time) .. 5; *small: the SMALL form of that flavour (small_rem, never with 0).
+// Level A: 1 .. 7, negative where level A has no kernel for the launch (fin_on, raw_input, or comb without an addend on both
+// polynomials).
+int hp_drop_flavour_b(const HpDropArgs &da, bool *small);
+int hp_drop_flavour_a(const HpDropArgs &da);
+
 namespace hp {
 struct ModConsts;
 }

@@ -19,16 +19,20 @@
 // The 64-bit patterns of the doubles travel through the same registers, LDS exchanges and table layouts as the integer kernels
 // (hp_ntt_tile.h); tables hold (w, u) as doubles (hp_tables.cpp: pairs_to_f64).  HBM rows stay u64 words: converted on load
 // (words must be below 2^52: every lazy word hehub or this engine produces is below 2 q <= 2^51) and on store.
+//
+// What is here: the FP64 butterfly policy (F64Bf), the load-side functors (ConvPre, DropPreA, DropPre2A), the range guard and the
+// FP64 arithmetic of the kernels' prologues and epilogues -- all of it under this file's -ffp-contract=off and the pragma below.
+// The pass schedule, geometry, loads, stores, staging, the drop epilogue's row pipeline and the launch dispatch are
+// hp_ntt_tile.h's, shared with hp_ntt_fast.hip.
 #include "hp_ntt_tile.h"
 
 #pragma clang fp contract(off)
 
+HP_TRACE_STORAGE(hp_debug_trace_a)
+
 namespace {
 
 typedef const HpLimbA __attribute__((address_space(4))) * cptr_limba;
-#ifdef HP_TRACE
-__device__ u64 g_trace[2 * 2048 * 16 * HP_TRACE_SLOTS];
-#endif
 
 HP_DEV double D(u64 v) { return __builtin_bit_cast(double, v); }
 HP_DEV u64 U(double d) { return __builtin_bit_cast(u64, d); }
@@ -166,56 +170,14 @@ template <int LOGN, bool SWAP, bool SCALE2> struct DropPre2A {
     }
 };
 
-// ---- passes: the slot schedule of hp_ntt_fast.hip (pass_slots) with the FP64 butterfly ---------------------------------------
-template <bool FWD, int S, int S0, int S1, int DEP, class Tab, class Pre = NoPre>
-HP_DEV void pass_slots_a(u64 (&x)[32], u64x2 (&ring)[DEP], const Tab &tbl, u32 ncls, u32 cls, double q, const Pre &pre = Pre()) {
-    if constexpr (S < S1) {
-        constexpr int cnt = 1 << (4 - ilog2c(S + 1));
-        constexpr int bit = slot_bit<FWD>(S);
-        const u64x2 tw = ring[(S - S0) % DEP];
-        if constexpr (S + DEP < S1) ring[(S - S0) % DEP] = tbl.at((u32)(S + DEP), ncls, cls);
-        if constexpr (cnt >= 2) {
-#pragma unroll
-            for (int o = 0; o < cnt; o += 2) {
-                const int ra = slot_reg<FWD>(S, o), rb = slot_reg<FWD>(S, o + 1);
-                if constexpr (Pre::on && S == 0) {
-                    static_assert(!Pre::on || (FWD && S0 == 0), "load-side work: first slot of a forward pass");
-                    pre(x, ra);
-                    pre(x, ra | bit);
-                }
-                a_bfly(x[ra], x[ra | bit], D(tw.x), D(tw.y), q);
-                a_bfly(x[rb], x[rb | bit], D(tw.x), D(tw.y), q);
-                if (o & 2) __builtin_amdgcn_sched_barrier(0);
-            }
-            if constexpr (cnt == 2) { if constexpr (S & 1) __builtin_amdgcn_sched_barrier(0); }
-            pass_slots_a<FWD, S + 1, S0, S1, DEP, Tab, Pre>(x, ring, tbl, ncls, cls, q, pre);
-        } else {
-            static_assert(S + 1 < S1, "single-butterfly slots come in pairs");
-            const u64x2 tw2 = ring[(S + 1 - S0) % DEP];
-            if constexpr (S + 1 + DEP < S1) ring[(S + 1 - S0) % DEP] = tbl.at((u32)(S + 1 + DEP), ncls, cls);
-            constexpr int ra = slot_reg<FWD>(S, 0), rb = slot_reg<FWD>(S + 1, 0);
-            a_bfly(x[ra], x[ra | bit], D(tw.x), D(tw.y), q);
-            a_bfly(x[rb], x[rb | bit], D(tw2.x), D(tw2.y), q);
-            if constexpr (((S - 15) & 2) != 0) __builtin_amdgcn_sched_barrier(0);
-            pass_slots_a<FWD, S + 2, S0, S1, DEP>(x, ring, tbl, ncls, cls, q);
-        }
+// the butterfly policy of pass_slots (hp_ntt_tile.h): two FP64 butterflies per call
+struct F64Bf {
+    double q;
+    template <bool SC> HP_DEV void pair(u64 &a0, u64 &a1, u64 &b0, u64 &b1, const u64x2 &ta, const u64x2 &tb) const {
+        a_bfly(a0, a1, D(ta.x), D(ta.y), q);
+        a_bfly(b0, b1, D(tb.x), D(tb.y), q);
     }
-}
-template <bool FWD, int S0, int S1, int DEP, class Tab, class Pre = NoPre>
-HP_DEV void run_pass_a(u64 (&x)[32], const Tab tbl, u32 ncls, u32 cls, double q, const Pre &pre = Pre()) {
-    u64x2 ring[DEP];
-#pragma unroll
-    for (int s = S0; s < S0 + DEP; ++s)
-        if (s < S1) ring[(s - S0) % DEP] = tbl.at((u32)s, ncls, cls);
-    pass_slots_a<FWD, S0, S0, S1, DEP, Tab, Pre>(x, ring, tbl, ncls, cls, q, pre);
-}
-template <int BLO, class Tab, class Pre = NoPre>
-HP_DEV void fwd_pass_a(u64 (&x)[32], const Tab tbl, u32 ncls, u32 cls, double q, const Pre &pre = Pre()) {
-    run_pass_a<true, 0, (1 << (5 - BLO)) - 1, Tab::depth, Tab, Pre>(x, tbl, ncls, cls, q, pre);
-}
-template <int BLO, class Tab> HP_DEV void inv_pass_a(u64 (&x)[32], const Tab tbl, u32 ncls, u32 cls, double q) {
-    run_pass_a<false, (1 << BLO) - 1, 31, Tab::depth>(x, tbl, ncls, cls, q);
-}
+};
 
 // ---- forward ---------------------------------------------------------------------------------------------------------------
 // FLAV (fused drop): 1 CKKS, no addend; 2 CKKS, addend on both polynomials (relinearize's +=, ckks/arith.cpp:70-71); 3 / 4 the
@@ -235,10 +197,10 @@ HP_DEV void ntt_fwd_a_body(const HpNttJob &job, const HpDropArgs *da) {
     const double q = lp->q, qinv = lp->qinv;
     const bool wide = lp->wide != 0;
     const u32 tid = threadIdx.x;
+    const F64Bf bf{q};
     AD ad;
     ad.init(tid);
-    u64v2 stg = {0, 0};
-    if (tid < 31u * (1u << G::A)) stg = ((gptr_u64x2)lp->fwd_k)[tid];
+    const u64v2 stg = fwd_stage_issue<LOGN>(lp, tid);
     TRACE_DECL
     TRACE_MARK();   // 0: decoded, staging load issued
     u64 x[32];
@@ -248,7 +210,7 @@ HP_DEV void ntt_fwd_a_body(const HpNttJob &job, const HpDropArgs *da) {
     DropPre2A<LOGN, SW, FLAV == 7> pre2;
     if constexpr (TWO) pre2.prime(da->comb + (size_t)it.poly * G::N, tid);
     load_flight<LOGN, SW>(it.src, tid, x);
-    if (tid < 31u * (1u << G::A)) lds_tw[tid] = stg;
+    fwd_stage_write<LOGN>(lds_tw, tid, stg);
     constexpr bool BGV = FLAV == 3 || FLAV == 4;
 #ifdef HP_TRACE
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -260,15 +222,15 @@ HP_DEV void ntt_fwd_a_body(const HpNttJob &job, const HpDropArgs *da) {
         pre2.q = q; pre2.p_last = D(da->dc.q_last); pre2.p_half = D(da->dc.half_q_last);
         pre2.q2_last = D(da->q2_last); pre2.q2_half = D(da->half_q2_last);
         pre2.m = D(da->dc.t[k]); pre2.mu = D(da->dc.t_h[k]); pre2.m2 = D(da->comb_mul[k]); pre2.m2u = D(da->comb_mul_h[k]);
-        fwd_pass_a<G::PB, STab>(x, STab(lp->fwd_ref + 1), 1u, 0u, q, pre2);
+        fwd_pass<4, G::PB, STab>(x, STab(lp->fwd_ref + 1), 1u, 0u, bf, pre2);
     } else if constexpr (DROP) {
         const u32 k = it.limb;
         const DropPreA<SW, BGV> pre{q, D(da->dc.q_last), D(da->dc.half_q_last), D(da->dc.t[k]), D(da->dc.t_h[k])};
-        fwd_pass_a<G::PB, STab>(x, STab(lp->fwd_ref + 1), 1u, 0u, q, pre);
+        fwd_pass<4, G::PB, STab>(x, STab(lp->fwd_ref + 1), 1u, 0u, bf, pre);
     } else {
         ConvPre<SW, SPREAD && !WORDS, !SPREAD> pre;
         pre.q = q; pre.qinv = qinv;
-        fwd_pass_a<G::PB, STab>(x, STab(lp->fwd_ref + 1), 1u, 0u, q, pre);
+        fwd_pass<4, G::PB, STab>(x, STab(lp->fwd_ref + 1), 1u, 0u, bf, pre);
         // N = 32768 reports after the exchange that follows (a divergent branch + two scalar loads here, where it has no SGPR to
         // spare, spilled 60 of them; carried to the end of the kernel the accumulator spilled 6 VGPRs); the smaller degrees report now
         if constexpr (LOGN == 15) guard = pre.acc;
@@ -280,13 +242,13 @@ HP_DEV void ntt_fwd_a_body(const HpNttJob &job, const HpDropArgs *da) {
     if (!DROP && !SPREAD && LOGN == 15) guard.report(lp);
     TRACE_MARK();   // 3
     // pass B: global stages A+1..A+5, twiddles depend on the 1024-block
-    fwd_pass_a<0>(x, LTab(lds_tw), 1u << G::A, tid >> 5, q);
+    fwd_pass<4, 0>(x, LTab(lds_tw), 1u << G::A, tid >> 5, bf);
     if (wide) a_reduce_all(x, qinv, q);
     TRACE_MARK();   // 4
     exchange<LOGN, LAY_B, LAY_C, false>(x, lds, ad);
     TRACE_MARK();   // 5
     // pass C: global stages A+6..logN, per-thread twiddles
-    fwd_pass_a<0>(x, BTab(lp->fwd_k + 31 * (1 << G::A)), (u32)G::T, tid, q);
+    fwd_pass<4, 0>(x, BTab(lp->fwd_k + 31 * (1 << G::A)), (u32)G::T, tid, bf);
     TRACE_MARK();   // 6
     if (!DROP) {
         if constexpr (SPREAD) {
@@ -309,84 +271,38 @@ HP_DEV void ntt_fwd_a_body(const HpNttJob &job, const HpDropArgs *da) {
     exchange<LOGN, LAY_C, LAY_S, false>(x, lds, ad);
     TRACE_MARK();   // 8
     if (!DROP) {
-        const size_t off = (((size_t)(tid >> 6)) << 11) + ((tid & 63u) << 1);
-        if (SPREAD && ((job.pack40_mask >> it.limb) & 1u)) {
-            typedef u32 __attribute__((ext_vector_type(2))) v2u;
-            u32 *lo = reinterpret_cast<u32 *>(it.dst) + off;
-            unsigned short *hi = reinterpret_cast<unsigned short *>(reinterpret_cast<char *>(it.dst) + 4 * (size_t)G::N + off);
-#pragma unroll
-            for (int s = 0; s < 16; ++s) {
-                __builtin_nontemporal_store(v2u{lo32(x[2 * s]), lo32(x[2 * s + 1])}, reinterpret_cast<v2u *>(lo + ((size_t)s << 7)));
-                __builtin_nontemporal_store((unsigned short)((hi32(x[2 * s]) & 0xffu) | ((hi32(x[2 * s + 1]) & 0xffu) << 8)), hi + ((size_t)s << 6));
-            }
-        } else if (SPREAD && ((job.pack_mask >> it.limb) & 1u)) {
-            // HP_PACK48 (hp_device.h): words below 3q/2 of a modulus below 2^47 always fit
-            typedef u32 __attribute__((ext_vector_type(2))) v2u;
-            u32 *lo = reinterpret_cast<u32 *>(it.dst) + off;
-            u32 *hi = reinterpret_cast<u32 *>(it.dst) + G::N + (off >> 1);
-#pragma unroll
-            for (int s = 0; s < 16; ++s) {
-                __builtin_nontemporal_store(v2u{lo32(x[2 * s]), lo32(x[2 * s + 1])}, reinterpret_cast<v2u *>(lo + ((size_t)s << 7)));
-                __builtin_nontemporal_store((hi32(x[2 * s]) & 0xffffu) | (hi32(x[2 * s + 1]) << 16), hi + ((size_t)s << 6));
-            }
-        } else {
-            u64 *d = it.dst + off;
-#pragma unroll
-            for (int s = 0; s < 16; ++s) {
-                V2 v{x[2 * s], x[2 * s + 1]};
-                st_stream(d + ((size_t)s << 7), v);
-            }
-        }
+        // (HP_PACK48: words below 3q/2 of a modulus below 2^47 always fit)
+        const size_t off = stream_off(tid);
+        if (SPREAD && ((job.pack40_mask >> it.limb) & 1u)) store_stream_pack40<LOGN>(it.dst, off, x);
+        else if (SPREAD && ((job.pack_mask >> it.limb) & 1u)) store_stream_pack48<LOGN>(it.dst, off, x);
+        else store_stream(it.dst, off, x);
     } else {
         // rescaling.cpp:72-74 / mod_switch.cpp:72-76 (+ the += of relinearize): ((x - NTT(rem)) * inv) [* (q_last mod t)] [+ addend]
         // as a residue: x and the addend are lazy words of the caller's rows (below 2^51), the result is canonical
-        const u32 k = it.limb, p2 = it.poly;
-        const u32 voff = ((((tid >> 6)) << 11) + ((tid & 63u) << 1)) << 3;
-        const bool has_add = FLAV == 2 || FLAV == 4 || TWO || (FLAV == 5 && __builtin_amdgcn_readfirstlane((p2 & 1u) == 0 ? 1 : 0) != 0);
-        const StreamBuf xs(da->x + ((size_t)p2 * da->L + k) * G::N);
-        const StreamBuf as(has_add ? da->addend + ((size_t)(p2 >> 1) * da->add_ct_stride + (size_t)(p2 & 1) * da->add_poly_stride + k) * G::N
-                                   : da->x);
-        const StreamBuf d(da->out + ((size_t)p2 * da->out_stride + k) * G::N);
+        const u32 k = it.limb;
+        const DropRows<LOGN, FLAV> io(da, k, it.poly, tid);
         const double inv = D(da->dc.inv[k]), invu = D(da->dc.inv_h[k]), ql = D(da->dc.qlt[k]), qlu = D(da->dc.qlt_h[k]);
-        RangeAcc acc;
-        auto rows = [&](auto add_tag) {
-            constexpr bool ADD = decltype(add_tag)::value;
-            constexpr int EPI_DEPTH = HP_EPI_DEPTH;
-            V2 xr[EPI_DEPTH], ar[EPI_DEPTH];
-#pragma unroll
-            for (int s = 0; s < EPI_DEPTH; ++s) {
-                xr[s] = xs.load(voff, (u32)s << 10);
-                if (ADD) ar[s] = as.load(voff, (u32)s << 10);
-            }
-#pragma unroll
-            for (int s = 0; s < 16; ++s) {
-                const V2 xv = xr[s % EPI_DEPTH];
-                V2 av{0, 0};
-                if (ADD) av = ar[s % EPI_DEPTH];
-                __builtin_amdgcn_sched_barrier(0);
-                if (s + EPI_DEPTH < 16) {
-                    xr[s % EPI_DEPTH] = xs.load(voff, (u32)(s + EPI_DEPTH) << 10);
-                    if (ADD) ar[s % EPI_DEPTH] = as.load(voff, (u32)(s + EPI_DEPTH) << 10);
+        const auto canon = [&](const V2 &v) { return V2{a_canon(D(v.x), qinv, q), a_canon(D(v.y), qinv, q)}; };   // rows compute doubles
+        if constexpr (TWO) {
+            // (the two-drop flavours only run inside the fused mult pipelines: their rows are the engine's own, lazy by construction)
+            // ((A x + a) - NTT(...)) B: |A x| <= q/2 (1 + 2^-1), a < 2^51, |NTT| < 1.12 * 2^50 (narrow limbs; q/2 for wide ones): below 2^52
+            io.run([&](auto, const V2 &xv, const V2 &av, int s) {
+                const double v0 = a_modmul(a_modmul(from_word(xv.x), inv, invu, q) + from_word(av.x) - D(x[2 * s]), ql, qlu, q);
+                const double v1 = a_modmul(a_modmul(from_word(xv.y), inv, invu, q) + from_word(av.y) - D(x[2 * s + 1]), ql, qlu, q);
+                return V2{U(v0), U(v1)};
+            }, canon);
+        } else {
+            RangeAcc acc;
+            io.run([&](auto add_tag, const V2 &xv, const V2 &av, int s) {
+                constexpr bool ADD = decltype(add_tag)::value;
+                acc.see(xv.x);
+                acc.see(xv.y);
+                if (ADD) {
+                    acc.see(av.x);
+                    acc.see(av.y);
                 }
-                __builtin_amdgcn_sched_barrier(0);
-                if (!TWO) {   // (the two-drop flavours only run inside the fused mult pipelines: their rows are the engine's own, lazy by construction)
-                    acc.see(xv.x);
-                    acc.see(xv.y);
-                    if (ADD) {
-                        acc.see(av.x);
-                        acc.see(av.y);
-                    }
-                }
-                double v0, v1;
-                if constexpr (TWO) {
-                    // ((A x + a) - NTT(...)) B: |A x| <= q/2 (1 + 2^-1), a < 2^51, |NTT| < 1.12 * 2^50 (narrow limbs; q/2 for wide ones): below 2^52
-                    v0 = a_modmul(a_modmul(from_word(xv.x), inv, invu, q) + from_word(av.x) - D(x[2 * s]), ql, qlu, q);
-                    v1 = a_modmul(a_modmul(from_word(xv.y), inv, invu, q) + from_word(av.y) - D(x[2 * s + 1]), ql, qlu, q);
-                    d.store(voff + ((u32)s << 10), V2{a_canon(v0, qinv, q), a_canon(v1, qinv, q)});
-                    continue;
-                }
-                v0 = a_modmul(from_word(xv.x) - D(x[2 * s]), inv, invu, q);
-                v1 = a_modmul(from_word(xv.y) - D(x[2 * s + 1]), inv, invu, q);
+                double v0 = a_modmul(from_word(xv.x) - D(x[2 * s]), inv, invu, q);
+                double v1 = a_modmul(from_word(xv.y) - D(x[2 * s + 1]), inv, invu, q);
                 if (BGV) {
                     v0 = a_modmul(v0, ql, qlu, q);
                     v1 = a_modmul(v1, ql, qlu, q);
@@ -395,14 +311,10 @@ HP_DEV void ntt_fwd_a_body(const HpNttJob &job, const HpDropArgs *da) {
                     v0 += from_word(av.x);
                     v1 += from_word(av.y);
                 }
-                d.store(voff + ((u32)s << 10), V2{a_canon(v0, qinv, q), a_canon(v1, qinv, q)});
-            }
-        };
-        if constexpr (FLAV == 2 || FLAV == 4 || TWO) rows(std::true_type{});
-        else if constexpr (FLAV == 1 || FLAV == 3) rows(std::false_type{});
-        else if (has_add) rows(std::true_type{});
-        else rows(std::false_type{});
-        if (!TWO) acc.report(lp);
+                return V2{U(v0), U(v1)};
+            }, canon);
+            acc.report(lp);
+        }
     }
     TRACE_MARK();   // 9: stores issued
     TRACE_FLUSH();
@@ -423,49 +335,28 @@ __global__ void __launch_bounds__(Geo<LOGN>::T, Geo<LOGN>::MINW) k_ntt_fwd_drop_
 }
 
 // ---- inverse (always returns canonical residues: intt_negacyclic_inplace of ntt.h:88-92) -----------------------------------
-template <int LOGN> struct InvGeoA {
-    static constexpr int LPW = LOGN >= 14 ? 1 : (512 >> (LOGN - 5));   // limbs of one modulus per workgroup (hp_ntt_fast.hip: InvGeo)
-    static constexpr int TT = Geo<LOGN>::T * LPW;
-    static constexpr bool STREAM_EPILOGUE = LOGN <= 13;
-};
-
 // MIX (the second coefficient row of drop_two_last_a in ONE launch): the coefficients modulo q' of y = A x + a - NTT(K cp), the row the
 // first drop would leave in the limb of q', are INTT(A x + a) - K cp by linearity: the input is combined from the row x and the addend
 // row a while loading, K times the centred coefficients of the previous drop is subtracted from the output
 template <int LOGN, bool PSCAL, bool MIX>
 HP_DEV void ntt_inv_a_body(const HpNttJob &job, const HpInvMixArgs *mx) {
     using G = Geo<LOGN>;
-    constexpr int LPW = InvGeoA<LOGN>::LPW, TT = InvGeoA<LOGN>::TT;
+    constexpr int LPW = InvGeo<LOGN>::LPW;
     __shared__ u32 lds_all[Addr<LOGN>::WORDS * LPW];
     __shared__ u64v2 lds_tw[31 * 32];
     const u32 sub = threadIdx.x / G::T, tid = threadIdx.x % G::T;
     u32 *lds = lds_all + sub * Addr<LOGN>::WORDS;
     HpItem it;
-    bool active = true;
-    if (LPW == 1) {
-        const u32 w = hp_xcd_remap(blockIdx.x, job.W);
-        const u32 k = w / job.P, p = w % job.P;
-        it.src = job.src + ((size_t)p * job.src_pstride + (size_t)k * job.src_kstride) * G::N;
-        it.dst = job.dst + ((size_t)p * job.dst_pstride + k) * G::N;
-        it.limb = k;
-        it.poly = p;
-    } else {
-        const u32 bpm = (job.P + LPW - 1) / LPW;
-        const u32 wb = hp_xcd_remap(blockIdx.x, job.L * bpm);
-        const u32 k = wb / bpm, p0 = (wb % bpm) * LPW + sub;
-        active = p0 < job.P;
-        const u32 p = active ? p0 : job.P - 1;
-        it.src = job.src + ((size_t)p * job.src_pstride + (size_t)k * job.src_kstride) * G::N;
-        it.dst = job.dst + ((size_t)p * job.dst_pstride + k) * G::N;
-        it.limb = k;
-        it.poly = p;
-    }
+    const bool active = inv_item<LOGN>(job, sub, it);
     const cptr_limba lp = (cptr_limba)(job.limbs_a + __builtin_amdgcn_readfirstlane(it.limb));
     const double q = lp->q, qinv = lp->qinv;
     const bool wide = lp->wide != 0;
+    const F64Bf bf{q};
     Addr<LOGN> ad;
     ad.init(tid);
-    constexpr int NSTG = (31 * 32 + TT - 1) / TT;
+    // (the twiddle staging, the stream load and the layout-A store of the inverse kernels stay written out in both files: as
+    // helpers of hp_ntt_tile.h each of them changed the instruction streams of the N <= 16384 kernels)
+    constexpr int TT = InvGeo<LOGN>::TT, NSTG = InvGeo<LOGN>::NSTG;
     u64v2 stg[NSTG];
 #pragma unroll
     for (int i = 0; i < NSTG; ++i) {
@@ -514,14 +405,14 @@ HP_DEV void ntt_inv_a_body(const HpNttJob &job, const HpInvMixArgs *mx) {
     }
     if (wide) a_reduce_all(x, qinv, q);   // lazy words up to 2 q
     exchange<LOGN, LAY_S, LAY_C, false>(x, lds, ad);
-    inv_pass_a<0>(x, STab(lp->inv_k), 1u, 0u, q);
+    inv_pass<0, 4>(x, STab(lp->inv_k), 1u, 0u, bf);
     if (wide) a_reduce_all(x, qinv, q);
     exchange<LOGN, LAY_C, LAY_B, false>(x, lds, ad);
     __syncthreads();   // the staged twiddles are read by other waves from here on
-    inv_pass_a<0>(x, LTab(lds_tw), 32u, tid & 31u, q);
+    inv_pass<0, 4>(x, LTab(lds_tw), 32u, tid & 31u, bf);
     if (wide) a_reduce_all(x, qinv, q);
     exchange<LOGN, LAY_B, LAY_A, true>(x, lds, ad);
-    inv_pass_a<G::PB>(x, BTab(lp->inv_k + 31 + 31 * 32), (u32)G::T, tid, q);
+    inv_pass<G::PB, 4>(x, BTab(lp->inv_k + 31 + 31 * 32), (u32)G::T, tid, bf);
     if (wide) a_reduce_all(x, qinv, q);
     const double psc = D(job.post_scalar), psu = D(job.post_scalar_h);
     // rows for a caller: words; rows for the digit-spread launch of the same key switch (job.dst_f64): the doubles themselves
@@ -536,7 +427,7 @@ HP_DEV void ntt_inv_a_body(const HpNttJob &job, const HpInvMixArgs *mx) {
         v -= a_modmul(c, mK, mKu, q);
         return PSCAL ? v : a_reduce(v, qinv, q);
     };
-    if constexpr (InvGeoA<LOGN>::STREAM_EPILOGUE) {
+    if constexpr (InvGeo<LOGN>::STREAM_EPILOGUE) {
         // N <= 8192: transpose once more so that the psi^-i N^-1 pairs are read and the words written 16 contiguous bytes per lane
         exchange<LOGN, LAY_A, LAY_S, true>(x, lds, ad);
         if (!active) return;
@@ -597,7 +488,7 @@ HP_DEV void ntt_inv_a_body(const HpNttJob &job, const HpInvMixArgs *mx) {
             __builtin_amdgcn_sched_barrier(0);
         }
         if (!active) return;
-        if (G::PB == 0) {
+        if (G::PB == 0) {   // mirror of the forward load: lane pairs assemble 16-byte stores
             const bool odd = (tid & 1u) != 0;
             u64 *dp = it.dst + (tid & ~1u);
 #pragma unroll
@@ -624,18 +515,18 @@ HP_DEV void ntt_inv_a_body(const HpNttJob &job, const HpInvMixArgs *mx) {
 }
 
 template <int LOGN, bool PSCAL>
-__global__ void __launch_bounds__(InvGeoA<LOGN>::TT, Geo<LOGN>::MINW) k_ntt_inv_a(HpNttJob job) {
+__global__ void __launch_bounds__(InvGeo<LOGN>::TT, Geo<LOGN>::MINW) k_ntt_inv_a(HpNttJob job) {
     ntt_inv_a_body<LOGN, PSCAL, false>(job, nullptr);
 }
 template <int LOGN, bool PSCAL>
-__global__ void __launch_bounds__(InvGeoA<LOGN>::TT, Geo<LOGN>::MINW) k_ntt_inv_mix_a(HpNttJob job, HpInvMixArgs mx) {
+__global__ void __launch_bounds__(InvGeo<LOGN>::TT, Geo<LOGN>::MINW) k_ntt_inv_mix_a(HpNttJob job, HpInvMixArgs mx) {
     ntt_inv_a_body<LOGN, PSCAL, true>(job, &mx);
 }
 
 template <int LOGN> hipError_t launch_inv_mix_a(const HpNttJob &job, const HpInvMixArgs &mx, hipStream_t stream) {
-    constexpr int LPW = InvGeoA<LOGN>::LPW, TT = InvGeoA<LOGN>::TT;
+    constexpr int TT = InvGeo<LOGN>::TT;
     if (!job.inverse || job.mode != HP_NTT_BATCH || job.pair_moduli || job.L != 1) return hipErrorNotSupported;
-    const u32 grid = LPW == 1 ? job.W : job.L * ((job.P + LPW - 1) / LPW);
+    const u32 grid = InvGeo<LOGN>::grid(job);
     if (job.use_post_scalar) k_ntt_inv_mix_a<LOGN, true><<<grid, TT, 0, stream>>>(job, mx);
     else k_ntt_inv_mix_a<LOGN, false><<<grid, TT, 0, stream>>>(job, mx);
     return hipGetLastError();
@@ -650,78 +541,37 @@ template <int LOGN> hipError_t launch_a(const HpNttJob &job, hipStream_t stream)
         else k_ntt_fwd_a<LOGN, false><<<job.W, Geo<LOGN>::T, 0, stream>>>(job);
         return hipGetLastError();
     }
-    constexpr int LPW = InvGeoA<LOGN>::LPW, TT = InvGeoA<LOGN>::TT;
+    constexpr int TT = InvGeo<LOGN>::TT;
     if (job.mode != HP_NTT_BATCH || job.pair_moduli) return hipErrorNotSupported;
-    const u32 grid = LPW == 1 ? job.W : job.L * ((job.P + LPW - 1) / LPW);
+    const u32 grid = InvGeo<LOGN>::grid(job);
     if (job.use_post_scalar) k_ntt_inv_a<LOGN, true><<<grid, TT, 0, stream>>>(job);
     else k_ntt_inv_a<LOGN, false><<<grid, TT, 0, stream>>>(job);
     return hipGetLastError();
 }
 
 template <int LOGN> hipError_t launch_drop_a(const HpNttJob &job, const HpDropArgs &da, hipStream_t stream) {
-    if (da.fin_on || da.raw_input) return hipErrorNotSupported;
-    int flav = 0;
-    if (da.comb) flav = (da.addend && da.add_mask == 3u) ? (da.dc.bgv ? 7 : 6) : 0;   // two drops at once
-    else if (!da.addend || da.add_mask == 0) flav = 1;
-    else if (da.add_mask == 3u) flav = 2;
-    else if (da.add_mask == 1u && !da.dc.bgv) flav = 5;
-    if (flav && flav < 5 && da.dc.bgv) flav += 2;
-#define HP_DROP_A(F) k_ntt_fwd_drop_a<LOGN, F><<<job.W, Geo<LOGN>::T, 0, stream>>>(job, da)
-    if (flav == 1) HP_DROP_A(1);
-    else if (flav == 2) HP_DROP_A(2);
-    else if (flav == 3) HP_DROP_A(3);
-    else if (flav == 4) HP_DROP_A(4);
-    else if (flav == 5) HP_DROP_A(5);
-    else if (flav == 6) HP_DROP_A(6);
-    else if (flav == 7) HP_DROP_A(7);
-    else return hipErrorNotSupported;
-#undef HP_DROP_A
-    return hipGetLastError();
+    const bool known = for_index<1, 7>(hp_drop_flavour_a(da), [&](auto f) {
+        k_ntt_fwd_drop_a<LOGN, decltype(f)::value><<<job.W, Geo<LOGN>::T, 0, stream>>>(job, da);
+    });
+    return known ? hipGetLastError() : hipErrorNotSupported;
 }
 
 } // namespace
 
-#ifdef HP_TRACE
-extern "C" int hp_debug_trace_a(u64 *out, size_t words) {
-    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_trace), words * sizeof(u64));
-}
-#endif
-
 hipError_t hp_launch_ntt_a(const HpNttJob &job, hipStream_t stream) {
     if (job.W == 0) return hipSuccess;
     if (!job.limbs_a) return hipErrorInvalidValue;
-    switch (job.logn) {
-    case 11: return launch_a<11>(job, stream);
-    case 12: return launch_a<12>(job, stream);
-    case 13: return launch_a<13>(job, stream);
-    case 14: return launch_a<14>(job, stream);
-    case 15: return launch_a<15>(job, stream);
-    default: return hipErrorNotSupported;
-    }
+    return for_logn(job, [&](auto n) { return launch_a<decltype(n)::value>(job, stream); });
 }
 
 hipError_t hp_launch_ntt_a_inv_mix(const HpNttJob &job, const HpInvMixArgs &mx, hipStream_t stream) {
     if (job.W == 0) return hipSuccess;
     if (!job.limbs_a) return hipErrorInvalidValue;
-    switch (job.logn) {
-    case 11: return launch_inv_mix_a<11>(job, mx, stream);
-    case 12: return launch_inv_mix_a<12>(job, mx, stream);
-    case 13: return launch_inv_mix_a<13>(job, mx, stream);
-    case 14: return launch_inv_mix_a<14>(job, mx, stream);
-    case 15: return launch_inv_mix_a<15>(job, mx, stream);
-    default: return hipErrorNotSupported;
-    }
+    return for_logn(job, [&](auto n) { return launch_inv_mix_a<decltype(n)::value>(job, mx, stream); });
 }
 
 hipError_t hp_launch_ntt_a_drop(const HpNttJob &job, const HpDropArgs &da, hipStream_t stream) {
     if (job.W == 0) return hipSuccess;
     if (!job.limbs_a) return hipErrorInvalidValue;
-    switch (job.logn) {
-    case 11: return launch_drop_a<11>(job, da, stream);
-    case 12: return launch_drop_a<12>(job, da, stream);
-    case 13: return launch_drop_a<13>(job, da, stream);
-    case 14: return launch_drop_a<14>(job, da, stream);
-    case 15: return launch_drop_a<15>(job, da, stream);
-    default: return hipErrorNotSupported;
-    }
+    return for_logn(job, [&](auto n) { return launch_drop_a<decltype(n)::value>(job, da, stream); });
 }

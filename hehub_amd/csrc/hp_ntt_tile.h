@@ -1,20 +1,25 @@
-// hp_ntt_tile.h -- the register / LDS tiling shared by the tiled transforms (hp_ntt_fast.hip: exact Harvey butterflies, parity
-// level B; hp_ntt_a.hip: error-free FP64 residue butterflies, parity level A): geometry, twiddle-table readers, LDS exchange
-// layouts, streaming HBM accesses, the forward kernel's load order.  See the head of hp_ntt_fast.hip for the schedule.
+// hp_ntt_tile.h -- everything of the tiled transforms that is not arithmetic, shared by hp_ntt_fast.hip (exact Harvey
+// butterflies, parity level B) and hp_ntt_a.hip (error-free FP64 residue butterflies, parity level A): geometry, twiddle-table
+// readers, LDS exchange layouts, the slot schedule of a pass over a butterfly policy, streaming HBM accesses, the forward kernels'
+// load, twiddle staging and stores, the inverse kernels' geometry and item decode, the row streams and software pipeline of the
+// fused drop epilogue, and the launch dispatch.  The two .hip files keep their butterfly policy, their Pre functors and the
+// arithmetic of their prologues and epilogues: no FP64 arithmetic here, it would be compiled under the other file's contraction
+// flags.  (The inverse kernels' staging, stream load and layout-A store are written out in both files: see there.)
+// See the head of hp_ntt_fast.hip for the schedule.
 #pragma once
 #include "hp_kernels.h"
 #include "hp_ntt_job.h"
 #include <type_traits>
+#include <utility>
 
 namespace {
-
 
 template <int LOGN> struct Geo {
     static constexpr int A = LOGN - 10;          // stages of pass A (1..5)
     static constexpr int PB = 5 - A;             // passenger bits of pass A's register index
     static constexpr int T = 1 << (LOGN - 5);    // threads per workgroup
     static constexpr int N = 1 << LOGN;
-    static constexpr int MINW = (T >= 1024) ? 4 : 4;   // waves per SIMD wanted (<= 128 VGPRs)
+    static constexpr int MINW = 4;                // waves per SIMD wanted (<= 128 VGPRs)
 };
 
 HP_DEV u32 lo32(u64 v) { return (u32)v; }
@@ -301,14 +306,78 @@ struct SwapPre {
     HP_DEV void operator()(u64 (&x)[32], int r) const { lazy_swap(x, r); }
 };
 
+// ---- the slot schedule of a pass, over a butterfly policy --------------------------------------
+// One slot (or, in the last stage of a pass where every butterfly has its own twiddle, two slots) of a pass;
+// recursion over the slot number keeps every register index a compile-time constant.
+// Bf: the arithmetic, `template <bool SCALAR_TAB> void pair(a0, a1, b0, b1, twA, twB) const` = two butterflies (a0, a1) with
+// twiddle pair twA and (b0, b1) with twB; it lives in the .hip file that owns the arithmetic (HarveyBf, F64Bf).
+// Pre (first pass of a forward kernel): work that belongs to the LOADS is done here, per register pair (r, r + 1) = one 16-byte
+// load, right before the first butterfly that touches it -- so the first stage runs while the later loads are still in flight
+// instead of after all sixteen (SwapPre above; DropPre, ConvPre, DropPreA, DropPre2A in the .hip files).
+// The scheduling barriers are placed by measurement: one misplaced barrier costs spills (128-VGPR budget).
+template <bool FWD, int S, int S0, int S1, int D, class Tab, class Bf, class Pre = NoPre>
+HP_DEV void pass_slots(u64 (&x)[32], u64x2 (&ring)[D], const Tab &tbl, u32 ncls, u32 cls, const Bf &bf, const Pre &pre = Pre()) {
+    if constexpr (S < S1) {
+        constexpr int cnt = 1 << (4 - ilog2c(S + 1));   // butterflies that use this slot's twiddle
+        constexpr int bit = slot_bit<FWD>(S);
+        const u64x2 tw = ring[(S - S0) % D];
+        if constexpr (S + D < S1) ring[(S - S0) % D] = tbl.at((u32)(S + D), ncls, cls);
+        if constexpr (cnt >= 2) {
+#pragma unroll
+            for (int o = 0; o < cnt; o += 2) {
+                const int ra = slot_reg<FWD>(S, o), rb = slot_reg<FWD>(S, o + 1);
+                if constexpr (Pre::on && S == 0) {
+                    static_assert(!Pre::on || (FWD && S0 == 0), "load-side work: first slot of a forward pass");
+                    pre(x, ra);          // rb == ra + 1: one 16-byte load
+                    pre(x, ra | bit);
+                }
+                bf.template pair<Tab::scalar>(x[ra], x[ra | bit], x[rb], x[rb | bit], tw, tw);
+                if (o & 2) __builtin_amdgcn_sched_barrier(0);
+            }
+            if constexpr (cnt == 2) { if constexpr (S & 1) __builtin_amdgcn_sched_barrier(0); }
+            pass_slots<FWD, S + 1, S0, S1, D, Tab, Bf, Pre>(x, ring, tbl, ncls, cls, bf, pre);
+        } else {
+            static_assert(S + 1 < S1, "single-butterfly slots come in pairs");
+            const u64x2 tw2 = ring[(S + 1 - S0) % D];
+            if constexpr (S + 1 + D < S1) ring[(S + 1 - S0) % D] = tbl.at((u32)(S + 1 + D), ncls, cls);
+            constexpr int ra = slot_reg<FWD>(S, 0), rb = slot_reg<FWD>(S + 1, 0);
+            bf.template pair<Tab::scalar>(x[ra], x[ra | bit], x[rb], x[rb | bit], tw, tw2);
+            if constexpr (((S - 15) & 2) != 0) __builtin_amdgcn_sched_barrier(0);
+            pass_slots<FWD, S + 2, S0, S1, D, Tab, Bf>(x, ring, tbl, ncls, cls, bf);
+        }
+    }
+}
+
+template <bool FWD, int S0, int S1, int D, class Tab, class Bf, class Pre = NoPre>
+HP_DEV void run_pass(u64 (&x)[32], const Tab tbl, u32 ncls, u32 cls, const Bf &bf, const Pre &pre = Pre()) {
+    u64x2 ring[D];
+#pragma unroll
+    for (int s = S0; s < S0 + D; ++s)
+        if (s < S1) ring[(s - S0) % D] = tbl.at((u32)s, ncls, cls);
+    pass_slots<FWD, S0, S0, S1, D, Tab, Bf, Pre>(x, ring, tbl, ncls, cls, bf, pre);
+}
+
+// forward: stages on register bits BHI..BLO (descending)
+template <int BHI, int BLO, class Tab, class Bf, class Pre = NoPre>
+HP_DEV void fwd_pass(u64 (&x)[32], const Tab tbl, u32 ncls, u32 cls, const Bf &bf, const Pre &pre = Pre()) {
+    static_assert(BHI == 4, "forward passes start at register bit 4");
+    run_pass<true, 0, (1 << (5 - BLO)) - 1, Tab::depth, Tab, Bf, Pre>(x, tbl, ncls, cls, bf, pre);
+}
+
+// inverse: stages on register bits BLO..BHI (ascending); D: depth of the twiddle ring
+template <int BLO, int BHI, class Tab, int D = Tab::depth, class Bf>
+HP_DEV void inv_pass(u64 (&x)[32], const Tab tbl, u32 ncls, u32 cls, const Bf &bf) {
+    static_assert(BHI == 4, "inverse passes end at register bit 4");
+    run_pass<false, (1 << BLO) - 1, 31, D, Tab, Bf>(x, tbl, ncls, cls, bf);
+}
+
 // ---- forward kernel ----------------------------------------------------------------------------
 #define HP_LOAD_ORDER(t) (((t) >> 1) | (((t) & 1) << 3))
 // load, layout A: thread reads 2^PB consecutive coefficients at 2^A places 1024 apart
 template <int LOGN, bool LZ = false>
 HP_DEV void load_flight(const u64 *src, u32 tid, u64 (&x)[32]) {
     using G = Geo<LOGN>;
-    const u64 *s = src + ((size_t)tid << G::PB);
-    if (G::PB == 0) {
+    if constexpr (G::PB == 0) {
         // N = 32768: a thread owns one column (tid) of 32 rows 1024 apart.  Two neighbouring lanes
         // fetch 16 bytes (both their columns) of alternate rows and trade halves with one DPP swap,
         // so every HBM instruction still moves 16 bytes per lane.
@@ -326,13 +395,12 @@ HP_DEV void load_flight(const u64 *src, u32 tid, u64 (&x)[32]) {
             x[2 * p] = odd ? recv : keep;
             x[2 * p + 1] = odd ? keep : recv;
         }
-    }
+    } else {
+        const u64 *s = src + ((size_t)tid << G::PB);
 #pragma unroll
-    for (int tk = 0; tk < (G::PB == 0 ? 0 : (1 << G::A)); ++tk) {
-        // same idea as above: the first stage pairs place kk with kk + 2^(A-1)
-        const int kk = (tk >> 1) | ((tk & 1) << (G::A - 1));
-        if (G::PB == 0) {
-        } else {
+        for (int tk = 0; tk < (1 << G::A); ++tk) {
+            // same idea as above: the first stage pairs place kk with kk + 2^(A-1)
+            const int kk = (tk >> 1) | ((tk & 1) << (G::A - 1));
 #pragma unroll
             for (int pp = 0; pp < (1 << G::PB); pp += 2) {
                 const V2 v = ld_stream(s + ((size_t)kk << 10) + pp);
@@ -343,9 +411,175 @@ HP_DEV void load_flight(const u64 *src, u32 tid, u64 (&x)[32]) {
     }
 }
 
-// Phase tracing for kernel tuning (the including .hip defines `__device__ u64 g_trace[2 * 2048 * 16 * HP_TRACE_SLOTS]` and exports a reader)
+// stage the forward middle pass's twiddles in LDS (31 * 2^A pairs, one per thread): the load is issued first, the LDS write after
+// the coefficient loads are in flight; it becomes visible through the barriers of the A->B exchange
+// (lp: the limb's constants, HpLimb or HpLimbA; the table pointer is read from it by the threads that stage, not before the branch)
+template <int LOGN, class LP> HP_DEV u64v2 fwd_stage_issue(LP lp, u32 tid) {
+    u64v2 stg = {0, 0};
+    if (tid < 31u * (1u << Geo<LOGN>::A)) stg = ((gptr_u64x2)lp->fwd_k)[tid];
+    return stg;
+}
+template <int LOGN> HP_DEV void fwd_stage_write(u64v2 *lds_tw, u32 tid, const u64v2 &stg) {
+    if (tid < 31u * (1u << Geo<LOGN>::A)) lds_tw[tid] = stg;
+}
+
+// word offset of a thread's 16 bytes in row 0 of layout S (row s is (s << 7) words further)
+HP_DEV size_t stream_off(u32 tid) { return (((size_t)(tid >> 6)) << 11) + ((tid & 63u) << 1); }
+
+// store, layout S: 16 bytes per lane, a wave writes 1 KiB of consecutive words per instruction
+HP_DEV void store_stream(u64 *dst, size_t off, const u64 (&x)[32]) {
+    u64 *d = dst + off;
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+        V2 v{x[2 * s], x[2 * s + 1]};
+        st_stream(d + ((size_t)s << 7), v);
+    }
+}
+// HP_PACK48 (hp_device.h): low words as 8 bytes per lane, high 16 bits of the two words as 4 bytes per lane
+template <int LOGN> HP_DEV void store_stream_pack48(u64 *dst, size_t off, const u64 (&x)[32]) {
+    typedef u32 __attribute__((ext_vector_type(2))) v2u;
+    u32 *lo = reinterpret_cast<u32 *>(dst) + off;
+    u32 *hi = reinterpret_cast<u32 *>(dst) + Geo<LOGN>::N + (off >> 1);
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+        __builtin_nontemporal_store(v2u{lo32(x[2 * s]), lo32(x[2 * s + 1])}, reinterpret_cast<v2u *>(lo + ((size_t)s << 7)));
+        __builtin_nontemporal_store((hi32(x[2 * s]) & 0xffffu) | (hi32(x[2 * s + 1]) << 16), hi + ((size_t)s << 6));
+    }
+}
+// HP_PACK40 (hp_device.h): low words as 8 bytes per lane, bits 32..39 of the two words as 2 bytes per lane
+template <int LOGN> HP_DEV void store_stream_pack40(u64 *dst, size_t off, const u64 (&x)[32]) {
+    typedef u32 __attribute__((ext_vector_type(2))) v2u;
+    u32 *lo = reinterpret_cast<u32 *>(dst) + off;
+    unsigned short *hi = reinterpret_cast<unsigned short *>(reinterpret_cast<char *>(dst) + 4 * (size_t)Geo<LOGN>::N + off);
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+        __builtin_nontemporal_store(v2u{lo32(x[2 * s]), lo32(x[2 * s + 1])}, reinterpret_cast<v2u *>(lo + ((size_t)s << 7)));
+        __builtin_nontemporal_store((unsigned short)((hi32(x[2 * s]) & 0xffu) | ((hi32(x[2 * s + 1]) & 0xffu) << 8)), hi + ((size_t)s << 6));
+    }
+}
+
+// ---- fused drop epilogue: rows x, addend and out of the thread's item, and the pipeline over their 16 rows ------------------
+// The three streams through buffer descriptors: one lane offset for all of them, the row step (s << 7 words) in an SGPR for the
+// loads, in the instruction's immediate / one 32-bit add for the stores -- no 64-bit address arithmetic on the vector ALU.
+// has_add is wave-uniform; said explicitly (readfirstlane) so that the run-time flavours branch on an SGPR instead of masking lanes:
+// flavour 0 asks add_mask, flavour 5 (rotations / conjugations, ckks/arith.cpp:75-93) adds the moved c0 to polynomial 0 only,
+// flavours 2 / 4 / 6 / 7 always add.
+template <int LOGN, int FLAV> struct DropRows {
+    using G = Geo<LOGN>;
+    u32 voff;
+    bool has_add;
+    StreamBuf xs, as, d;
+    HP_DEV DropRows(const HpDropArgs *da, u32 k, u32 p2, u32 tid)
+        : voff(((((tid >> 6)) << 11) + ((tid & 63u) << 1)) << 3),
+          has_add(FLAV == 2 || FLAV == 4 || FLAV == 6 || FLAV == 7 || (FLAV == 5 && __builtin_amdgcn_readfirstlane((p2 & 1u) == 0 ? 1 : 0) != 0) ||
+                  (FLAV == 0 && __builtin_amdgcn_readfirstlane((da->addend && ((da->add_mask >> (p2 & 1)) & 1u)) ? 1 : 0) != 0)),
+          xs(da->x + ((size_t)p2 * da->L + k) * G::N),
+          as(has_add ? da->addend + ((size_t)(p2 >> 1) * da->add_ct_stride + (size_t)(p2 & 1) * da->add_poly_stride + k) * G::N : da->x),
+          d(da->out + ((size_t)p2 * da->out_stride + k) * G::N) {}
+
+    // The 16 rows are software-pipelined by hand: the operand loads run HP_EPI_DEPTH rows ahead of their use (ring in
+    // registers, the twiddle ring is dead by now), otherwise every row waits for its own two loads with
+    // vmcnt(0) -- which also drains the stores of the previous row -- and the epilogue costs 32 exposed round trips.
+    // row(add_tag, x_row, add_row, s) -> the result of row s (registers 2 s, 2 s + 1 of the transform); words(result) -> the words
+    // stored (level A: the canonical residues of its doubles), evaluated after the store's offset as both files always had it
+    template <bool ADD, class Row, class Words> HP_DEV void pipeline(const Row &row, const Words &words) const {
+        constexpr int EPI_DEPTH = HP_EPI_DEPTH;
+        V2 xr[EPI_DEPTH], ar[EPI_DEPTH];
+#pragma unroll
+        for (int s = 0; s < EPI_DEPTH; ++s) {
+            xr[s] = xs.load(voff, (u32)s << 10);
+            if (ADD) ar[s] = as.load(voff, (u32)s << 10);
+        }
+#pragma unroll
+        for (int s = 0; s < 16; ++s) {
+            const V2 xv = xr[s % EPI_DEPTH];
+            V2 av{0, 0};
+            if (ADD) av = ar[s % EPI_DEPTH];
+            __builtin_amdgcn_sched_barrier(0);
+            if (s + EPI_DEPTH < 16) {
+                xr[s % EPI_DEPTH] = xs.load(voff, (u32)(s + EPI_DEPTH) << 10);
+                if (ADD) ar[s % EPI_DEPTH] = as.load(voff, (u32)(s + EPI_DEPTH) << 10);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            const V2 out = row(std::bool_constant<ADD>{}, xv, av, s);
+            d.store(voff + ((u32)s << 10), words(out));
+        }
+    }
+    // one copy of the row loop per value of has_add where it is only known at run time (flavours 0 and 5): the loop body
+    // then has no branch on it
+    template <class Row, class Words> HP_DEV void run(const Row &row, const Words &words) const {
+        if constexpr (FLAV == 2 || FLAV == 4 || FLAV == 6 || FLAV == 7) pipeline<true>(row, words);
+        else if constexpr (FLAV == 1 || FLAV == 3) pipeline<false>(row, words);
+        else if (has_add) pipeline<true>(row, words);
+        else pipeline<false>(row, words);
+    }
+};
+
+// ---- inverse kernels -------------------------------------------------------------------------------
+// The middle pass of the inverse stages 31 x 32 twiddle pairs (15.5 KiB) in LDS whatever N is.  With one limb per workgroup
+// that stage caps the occupancy of the small sizes (N = 4096: 16 + 15.5 KiB per two waves -> 5 workgroups = 2.5 waves per
+// SIMD, VALUBusy 42 %).  So for N <= 8192 a workgroup transforms LPW limbs OF ONE MODULUS side by side and shares the stage:
+// 512 threads, 4 N LPW + 15.5 KiB = 80 KiB of LDS, two workgroups = four waves per SIMD on a CU.
+template <int LOGN> struct InvGeo {
+    static constexpr int LPW = LOGN >= 14 ? 1 : (512 >> (LOGN - 5));   // limbs per workgroup: 2^11 -> 8, 2^12 -> 4, 2^13 -> 2
+    static constexpr int TT = Geo<LOGN>::T * LPW;                      // threads per workgroup
+    static constexpr bool STREAM_EPILOGUE = LOGN <= 13;                // see the end of k_ntt_inv
+    static constexpr int NSTG = (31 * 32 + TT - 1) / TT;               // staged twiddle pairs per thread
+    static u32 grid(const HpNttJob &job) { return LPW == 1 ? job.W : job.L * ((job.P + LPW - 1) / LPW); }
+};
+
+// the item of sub-limb `sub` of a workgroup; false: a group past the last polynomial, which re-reads the last one and stores nothing
+// (every inverse launch is HP_NTT_BATCH without groups: the launchers reject anything else)
+template <int LOGN> HP_DEV bool inv_item(const HpNttJob &job, u32 sub, HpItem &it) {
+    using G = Geo<LOGN>;
+    constexpr int LPW = InvGeo<LOGN>::LPW;
+    bool active = true;
+    if (LPW == 1) {
+        const u32 w = hp_xcd_remap(blockIdx.x, job.W);
+        const u32 k = w / job.P, p = w % job.P;
+        it.src = job.src + ((size_t)p * job.src_pstride + (size_t)k * job.src_kstride) * G::N;
+        it.dst = job.dst + ((size_t)p * job.dst_pstride + k) * G::N;
+        it.limb = k;
+        it.poly = p;
+    } else {
+        // ceil(P / LPW) workgroups per modulus, modulus-major like the item numbering
+        const u32 bpm = (job.P + LPW - 1) / LPW;
+        const u32 wb = hp_xcd_remap(blockIdx.x, job.L * bpm);
+        const u32 k = wb / bpm, p0 = (wb % bpm) * LPW + sub;
+        active = p0 < job.P;
+        const u32 p = active ? p0 : job.P - 1;
+        it.src = job.src + ((size_t)p * job.src_pstride + (size_t)k * job.src_kstride) * G::N;
+        it.dst = job.dst + ((size_t)p * job.dst_pstride + k) * G::N;
+        it.limb = k;
+        it.poly = p;
+    }
+    return active;
+}
+
+// ---- launch dispatch -------------------------------------------------------------------------------
+// f(std::integral_constant<int, LOGN>) for the ring degrees the tiled kernels are built for
+template <class F> hipError_t for_logn(const HpNttJob &job, F f) {
+    switch (job.logn) {
+    case 11: return f(std::integral_constant<int, 11>{});
+    case 12: return f(std::integral_constant<int, 12>{});
+    case 13: return f(std::integral_constant<int, 13>{});
+    case 14: return f(std::integral_constant<int, 14>{});
+    case 15: return f(std::integral_constant<int, 15>{});
+    default: return hipErrorNotSupported;
+    }
+}
+// f(std::integral_constant<int, I>) for the I of LO .. HI that equals i; false: none does
+template <int LO, int HI, class F> bool for_index(int i, F f) {
+    if constexpr (LO <= HI) {
+        if (i == LO) { f(std::integral_constant<int, LO>{}); return true; }
+        return for_index<LO + 1, HI>(i, f);
+    }
+    return false;
+}
+
 // Phase tracing for kernel tuning (variant builds only, -DHP_TRACE): shader-clock stamps of wave 0
-// of every 16th workgroup at the phase boundaries, read back with hp_debug_trace().
+// of every 16th workgroup at the phase boundaries.  Each .hip file says HP_TRACE_STORAGE(reader) once, at file scope before its
+// kernels: its own g_trace and the exported reader (hp_debug_trace, hp_debug_trace_a).
 #ifdef HP_TRACE
 #ifdef HP_TRACE_ALL
 #define HP_TRACE_SEL (blockIdx.x < 2048 * 16)
@@ -355,6 +589,9 @@ HP_DEV void load_flight(const u64 *src, u32 tid, u64 (&x)[32]) {
 #define HP_TRACE_IDX (blockIdx.x >> 4)
 #endif
 #define HP_TRACE_SLOTS 12
+#define HP_TRACE_STORAGE(reader) \
+    namespace { __device__ u64 g_trace[2 * 2048 * 16 * HP_TRACE_SLOTS]; } \
+    extern "C" int reader(u64 *out, size_t words) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_trace), words * sizeof(u64)); }
 #define TRACE_DECL u64 tr__[HP_TRACE_SLOTS]; int tri__ = 0; tr__[10] = ((u64)__builtin_amdgcn_s_getreg(63492) << 32) | (u32)__builtin_amdgcn_s_getreg((31 << 11) | 20); tr__[11] = t_entry__;
 #define TRACE_ENTRY __builtin_amdgcn_sched_barrier(0); const u64 t_entry__ = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0);
 #define TRACE_MARK() do { __builtin_amdgcn_sched_barrier(0); tr__[tri__++] = __builtin_amdgcn_s_memtime(); __builtin_amdgcn_sched_barrier(0); } while (0)
@@ -366,6 +603,7 @@ HP_DEV void load_flight(const u64 *src, u32 tid, u64 (&x)[32]) {
         for (int i__ = 0; i__ < HP_TRACE_SLOTS; i__++) g_trace[(HP_TRACE_IDX * 2 + (threadIdx.x != 0)) * HP_TRACE_SLOTS + i__] = (i__ < tri__ || i__ >= 10) ? tr__[i__] : 0; } } while (0)
 #endif
 #else
+#define HP_TRACE_STORAGE(reader)
 #define TRACE_DECL
 #define TRACE_ENTRY
 #define TRACE_MARK() do { } while (0)

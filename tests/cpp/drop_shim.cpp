@@ -86,6 +86,18 @@ void ds_hks_down(const uint64_t *mext, size_t L, size_t k, size_t i0, size_t cnt
     dump(da, out);
 }
 
+// the kernel flavour of a launch with these fields set (everything else zero): out2 = {level B flavour, its SMALL flag}; returns level A's
+int ds_flavours(int fin_on, int raw_input, int comb, int addend, unsigned add_mask, int bgv, int small_rem, int *out2) {
+    static const u64 row[1] = {0};
+    HpDropArgs da = blank();
+    da.fin_on = fin_on; da.raw_input = raw_input; da.comb = comb ? row : nullptr; da.addend = addend ? row : nullptr;
+    da.add_mask = add_mask; da.dc.bgv = bgv; da.small_rem = small_rem;
+    bool small = false;
+    out2[0] = hp_drop_flavour_b(da, &small);
+    out2[1] = small ? 1 : 0;
+    return hp_drop_flavour_a(da);
+}
+
 void ds_hks_down_rescale(const uint64_t *mext, size_t L, size_t k, uint64_t comb, int level_a, uint64_t *out) {
     HksLimbConsts h;
     hks_limb_consts(mext, L, k, h);

@@ -50,6 +50,7 @@ def ds():
     lib.ds_hks_limbs.argtypes = [p, z, z, p]
     lib.ds_hks_down.argtypes = [p, z, z, z, z, i, p]
     lib.ds_hks_down_rescale.argtypes = [p, z, z, u, i, p]
+    lib.ds_flavours.argtypes = [i, i, i, i, C.c_uint, i, i, p]
     assert lib.ds_max_limbs() == ML
     return lib
 
@@ -273,3 +274,45 @@ def test_hybrid(ds, shape):
 def test_hybrid_rejects_a_special_prime_that_is_a_ciphertext_modulus(ds):
     out = np.zeros(8, dtype=np.uint64)
     assert ds.ds_hks_limbs(ptr(arr([P.P40[0], P.P40[1], P.P40[0]])), 2, 1, ptr(out)) == 0
+
+
+# ---- which compiled flavour a launch takes (hp_drop_flavour_b / hp_drop_flavour_a) -----------------------------------------------
+# level B, without fin_on / raw_input / comb: by (addend in effect, add_mask, bgv); everything else is the run-time flavour 0
+FLAV_B = {("none", 0): 1, ("none", 1): 3,      # no addend (no rows, or mask 0): rescale / mod_switch
+          (3, 0): 2, (3, 1): 4,                # both polynomials: relinearize
+          (1, 0): 5, (1, 1): 0,                # polynomial 0 only: rotation (CKKS); BGV has no such kernel
+          (2, 0): 0, (2, 1): 0}                # polynomial 1 only: no such kernel
+# level A: no kernel at all for fin_on / raw_input, nor for comb without an addend on both polynomials
+FLAV_A = {("none", 0): 1, ("none", 1): 3, (3, 0): 2, (3, 1): 4, (1, 0): 5, (1, 1): -1, (2, 0): -1, (2, 1): -1}
+FLAV_A_TWO = {0: 6, 1: 7}                      # comb and addend on both polynomials: two drops in one transform, CKKS / BGV
+
+
+def test_flavour_tables(ds):
+    seen_b, seen_a = set(), set()
+    for fin_on in (0, 1):
+        for raw_input in (0, 1):
+            for comb in (0, 1):
+                for addend in (0, 1):
+                    for mask in (0, 1, 2, 3):
+                        for bgv in (0, 1):
+                            for small_rem in (0, 1):
+                                out = np.zeros(2, dtype=np.int32)
+                                fa = ds.ds_flavours(fin_on, raw_input, comb, addend, mask, bgv, small_rem, ptr(out))
+                                fb, small = int(out[0]), int(out[1])
+                                add = mask if addend and mask else "none"
+                                exp_b = 0 if fin_on or raw_input or comb else FLAV_B[(add, bgv)]
+                                if fin_on or raw_input:
+                                    exp_a = -1
+                                elif comb:
+                                    exp_a = FLAV_A_TWO[bgv] if add == 3 else -1
+                                else:
+                                    exp_a = FLAV_A[(add, bgv)]
+                                case = (fin_on, raw_input, comb, addend, mask, bgv, small_rem)
+                                assert fb == exp_b and small == int(exp_b != 0 and small_rem == 1), case
+                                assert fa == exp_a if exp_a > 0 else fa < 0, case
+                                seen_b.add((fb, small)); seen_a.add(max(fa, -1))
+    assert seen_b == {(0, 0)} | {(f, s) for f in range(1, 6) for s in (0, 1)} and seen_a == {-1, 1, 2, 3, 4, 5, 6, 7}
+    # spelled out: the launches that fall to flavour 0 at level B although nothing run-time-only is asked for
+    for mask, bgv in ((2, 0), (2, 1), (1, 1)):
+        out = np.zeros(2, dtype=np.int32)
+        assert ds.ds_flavours(0, 0, 0, 1, mask, bgv, 1, ptr(out)) < 0 and (int(out[0]), int(out[1])) == (0, 0)
