@@ -353,6 +353,65 @@ extern "C" int hp_dev_ckks_rotate_hoisted_hks(hp_ctx *ctx, size_t logn, size_t L
     return HP_OK;
 }
 
+// Diagonal linear transform, double hoisted: out = sum_r diag_r * rot_r(ct) with one key per rotation, the weighted sum formed in the
+// extended basis Q P BEFORE ModDown.  Everything after the inner product of a switch is linear in its accumulator, so
+//   sum_r diag_r * ModDown(acc_r)  ~  ModDown( sum_r diag_r * acc_r )
+// up to the roundings: R of them, each scaled by its diagonal, on the left; ONE on the right.  The flow is that of a single switch of
+// `batch` polynomials -- hks_digits, the accumulate launches (k_hks_inner_lintrans, at most one argument table of rotations each, the
+// later ones adding to the reduced words of the earlier), hks_pdown, hks_down -- and so is the workspace, whatever `rotations` is:
+// no [b][r] row set, no yp / rem per rotation, no moved c0 (the kernel folds (P mod q_i) diag_r move_r(c0) into polynomial 0 of the
+// accumulator, which ModDown divides by P exactly: hks_down runs without an addend).
+extern "C" int hp_dev_ckks_lintrans_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                        size_t batch, size_t rotations, const size_t *steps, const unsigned char *conj, const uint64_t *ct,
+                                        const uint64_t *const *keys, const uint64_t *const *diags, uint64_t *out) {
+    HP_ENTER(ctx);
+    HP_REQUIRE(ctx, moduli_ext, steps, ct, keys, diags, out);
+    HP_ALIGNED(ctx, ct, out);
+    int rc = hks_args_ok(ctx, logn, L, k, alpha, batch);
+    if (rc) return rc;
+    if (rotations == 0) return fail(ctx, HP_EINVAL, "lintrans: no rotations");
+    for (size_t r = 0; r < rotations; r++) {
+        if (!keys[r] || ((uintptr_t)keys[r] & 15u)) return fail(ctx, HP_EINVAL, "lintrans: NULL or misaligned key");
+        if ((uintptr_t)diags[r] & 15u) return fail(ctx, HP_EINVAL, "lintrans: misaligned diagonal");
+        if (!(conj && conj[r]) && steps[r] >= ((size_t)1 << 17)) return fail(ctx, HP_EINVAL, "rotation step out of range");
+    }
+    const size_t n = (size_t)1 << logn, E = L + k, nd = (L + alpha - 1) / alpha;
+    {
+        const uintptr_t c0 = (uintptr_t)ct, o0 = (uintptr_t)out, bytes = batch * 2 * L * n * 8;
+        if (o0 < c0 + bytes && c0 < o0 + bytes) return fail(ctx, HP_EINVAL, "lintrans: the output overlaps the input");
+    }
+    const size_t pass = hks_lintrans_max_rotations(moduli_ext, E, nd, HP_HOIST_TABLE_MAX);   // rotations per launch
+    if (pass == 0) return fail(ctx, HP_EUNSUPPORTED, "lintrans: moduli too large for the 128-bit accumulators");
+    const Plan *plan;
+    if ((rc = get_plan(ctx, logn, moduli_ext, E, true, &plan))) return rc;
+    const HksEntry *he;
+    if ((rc = get_hks_consts(ctx, moduli_ext, L, k, alpha, &he))) return rc;
+    LevelScope lvl(ctx, plan);   // level A: the digit stage and the drops on the FP64 kernels, as in hp_dev_hks_switch
+    if (lvl.rc) return lvl.rc;
+    if ((rc = ws_reserve(ctx, hks_ws_words(n, L, k, nd, batch) * 8))) return rc;
+    Carver cv(ctx->ws);
+    u64 *lifted;
+    if ((rc = hks_digits(ctx, plan, he->dev, logn, L, k, alpha, batch, ct + L * n, 2 * L, &lifted, cv))) return rc;
+    u64 *ks = cv.take(batch * 2 * E * n), *yp = cv.take(2 * batch * k * n), *rem = cv.take(2 * batch * L * n);
+    for (size_t r0 = 0; r0 < rotations; r0 += pass) {
+        const size_t cnt = std::min(pass, rotations - r0);
+        HpLinTable ht;
+        memset(&ht, 0, sizeof(ht));
+        if ((rc = reserve_cycle_perms(ctx, cnt))) return rc;   // (a miss in a full map cache empties it: not between these)
+        for (size_t r = 0; r < cnt; r++) {
+            ht.key[r] = keys[r0 + r];
+            ht.diag[r] = diags[r0 + r];
+            if (!(conj && conj[r0 + r]) && (rc = get_cycle_perm(ctx, logn, steps[r0 + r], &ht.map[r]))) return rc;
+        }
+        ProfScope ps(ctx, "ks_inner");
+        if ((rc = chk(ctx, hp_launch_hks_inner_lintrans(plan->d_limbs, he->dev, (u32)E, (u32)n, (u32)batch, (u32)cnt, lifted, ct, ht, r0 != 0,
+                                                        ks, ctx->stream), "hks_inner_lintrans")))
+            return rc;
+    }
+    if ((rc = hks_pdown(ctx, plan, he->dev, logn, L, k, batch, ks, moduli_ext, yp, rem))) return rc;
+    return hks_down(ctx, plan, he, logn, L, k, batch, ks, rem, Addend(), moduli_ext, out);
+}
+
 // ckks::mult_low_level + relinearisation with a hybrid key + rescale by the last ciphertext modulus
 extern "C" int hp_dev_ckks_mult_relin_rescale_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
                                        size_t batch, const uint64_t *ct1, const uint64_t *ct2, const uint64_t *key,

@@ -4,6 +4,7 @@
 
 #include "hp_tables.h"
 
+#include <algorithm>
 #include <cstring>
 
 int hp_drop_flavour_b(const HpDropArgs &da, bool *small) {
@@ -140,6 +141,17 @@ bool hks_limb_consts(const u64 *mext, size_t L, size_t k, HksLimbConsts &out) {
         harvey_pair(inv_mod(pm, q), q, out.pinv[i], out.pinv_h[i]);
     }
     return true;
+}
+
+size_t hks_lintrans_max_rotations(const u64 *mext, size_t E, size_t nd, size_t table_max) {
+    typedef unsigned __int128 u128;
+    u64 q = 0;
+    for (size_t m = 0; m < E; m++) q = std::max(q, mext[m]);
+    if (q == 0 || q >> 62) return 0;   // (2q must leave room in a word; keeps everything below inside 128 bits)
+    const u128 t = (((u128)q * q) >> 64) + 1, w = 4 * (u128)nd * t + 3 * (u128)q;
+    if (w >> 64) return 0;
+    const u128 r = ~(u128)0 / (w * (2 * (u128)q));
+    return r < table_max ? (size_t)r : table_max;
 }
 
 void a_raw_rows(HpDropArgs &da) {

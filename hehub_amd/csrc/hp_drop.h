@@ -141,6 +141,11 @@ struct HksLimbConsts {   // per ciphertext modulus q_i, with Harvey words
     std::vector<u64> p_mod_q, p_mod_q_h;   // P mod q_i
 };
 bool hks_limb_consts(const u64 *mext, size_t L, size_t k, HksLimbConsts &out);   // false: some q_i divides P
+// How many rotations one launch of k_hks_inner_lintrans (hp_hks.hip) may sum before its 128-bit accumulators could wrap, at most
+// table_max; 0: not even one.  With q the largest modulus of the chain and nd digits, a rotation's word (the Montgomery word of nd
+// products of lazy words, plus the folded c0 term) is below w = 4 nd ceil(q^2 / 2^64) + 3q, which must be a 64-bit word, and a
+// diagonal word below 2q: the largest R with R w 2q < 2^128.  Exact integers.
+size_t hks_lintrans_max_rotations(const u64 *mext, size_t E, size_t nd, size_t table_max);
 // level A: the transform's input rows ARE the remainders -- centring against a threshold out of reach (2^62) does nothing
 void a_raw_rows(HpDropArgs &da);
 // ModDown of the limbs [i0, i0 + cnt): out = (x - NTT(rem)) P^-1 [+ addend]; level B, then that block to level A

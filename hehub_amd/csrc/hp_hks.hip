@@ -207,6 +207,115 @@ hipError_t hp_launch_hks_inner_hoisted(const HpLimb *limbs, u32 L, u32 E, u32 nd
     return hipGetLastError();
 }
 
+// Diagonal linear transform in the extended basis (hp_dev_ckks_lintrans_hks): k_hks_inner_hoisted with the rotation loop INSIDE the
+// thread.  A thread owns one pair of words of acc[b][.][m] and, for every rotation r of the table, runs the digit loop of the hoisted
+// kernel (the map's pair or the swapped 16 bytes of the involution; cached digit loads; non-temporal key loads), reduces the digit sum
+// to a word w_r (Montgomery: the keys carry the 2^64) and multiplies it by the diagonal's word into a SECOND set of carry-save columns:
+//   acc[b][h][m][i] = sum_r diag_r[m][i] * w_r,      w_r = montgomery_128( sum_d D[b][d][m][map_r(i)] * key_r[d][h][m][i] )
+// The diagonals are plain words, so the one Montgomery reduction of the outer sum leaves a factor 2^-64.  It is undone by a Harvey
+// multiplication by 2^64 mod q with the limb's own pair (r64, r64h) -- hp_mul_hybrid_lazy's tail: one high and two low products per
+// OUTPUT word, no new constant, and its result is below 2q for any 64-bit input, which is what the level-A range guard and the drops
+// ask of these rows.  (A Montgomery multiplication by 2^128 mod q costs one more product and a new per-limb constant.)
+// The c0 term of the rotation is folded in rather than kept as a third accumulator and an addend row: on polynomial 0 and the
+// ciphertext moduli the word (P mod q) * map_r(c0) is added to w_r before the diagonal multiplies it -- ModDown divides P out exactly
+// and the special-prime limbs see a multiple of P, i.e. nothing.  One gathered load and one Harvey product per rotation on 1/(2(1+k/L))
+// of the rows, against 8 more VGPRs per word and an addend row written and read.
+// Ranges: w_r + the folded word < 4 nd ceil(q^2 / 2^64) + 3q, times a diagonal word < 2q, summed over R: the host keeps that below
+// 2^128 (hpi::hks_lintrans_max_rotations, hp_drop.h: 32 rotations for every modulus below 2^59).  A diagonal word of 2q or more can
+// make the sum wrap unnoticed: the residues are then undefined.
+// Workgroups: one pair per thread (chunks of 2 * ELEM_THREADS words -- the rotations no longer widen the grid), units = (modulus,
+// ciphertext) numbered by XCD as in the hoisted kernel: the digit rows of a unit are now read R times by the SAME workgroups.
+// Unmeasured for this kernel.  One ciphertext per thread at every batch: two sets of accumulators already leave 4 waves per SIMD.
+#define HKS_LT_CHUNK (2u * ELEM_THREADS)
+__global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner_lintrans(const HpLimb *__restrict__ limbs, const HpHksConsts *__restrict__ hc,
+                                                                   u32 P, u32 R, u32 n, u32 chunks, const u64 *__restrict__ lifted,
+                                                                   const u64 *__restrict__ ct, HpLinTable tab, u32 add_prev,
+                                                                   u64 *__restrict__ out) {
+    const u32 L = hc->L, E = hc->E, nd = hc->nd, alpha = hc->alpha;
+    const u32 units = E * P, W = chunks, grouped = (units & ~7u) * W;
+    u32 unit, w;
+    if (blockIdx.x < grouped) {
+        unit = (blockIdx.x / (8 * W)) * 8 + (blockIdx.x & 7u);
+        w = (blockIdx.x >> 3) % W;
+    } else {
+        unit = (units & ~7u) + (blockIdx.x - grouped) / W;
+        w = (blockIdx.x - grouped) % W;
+    }
+    const u32 m = unit / P, p = unit % P;
+    const ElemTile tile(ElemTile::At{unit, w}, n, HKS_LT_CHUNK);
+    const u64 q = limbs[m].q, mqinv = limbs[m].mqinv, two_q = limbs[m].two_q, r64 = limbs[m].r64, r64h = limbs[m].r64h;
+    const u32 own = (m < L) ? m / alpha : nd;   // the digit this modulus belongs to (none for the special primes)
+    const bool fold = m < L;                    // polynomial 0 of these rows takes the c0 term
+    const u64 pm = fold ? hc->p_mod_q[m] : 0, pmh = fold ? hc->p_mod_q_h[m] : 0;
+    const u64 *__restrict__ c0row = ct + ((size_t)p * 2 * L + m) * n;   // a ciphertext is 2 L rows: c0, then c1
+    const u64 *__restrict__ c1row = c0row + (size_t)L * n;
+    for (const u32 i : tile.pairs()) {
+        HpAcc sum[2][2];   // the outer sum over the rotations
+#pragma unroll
+        for (int h = 0; h < 2; h++) { hp_acc_zero(sum[h][0]); hp_acc_zero(sum[h][1]); }
+        for (u32 r = 0; r < R; r++) {
+            const u64 *__restrict__ key = tab.key[r];
+            const u32 *__restrict__ map = tab.map[r];   // NULL: the involution i -> n - 1 - i
+            const u64 *__restrict__ dg = tab.diag[r];   // NULL: the constant 1
+            // where the two digit words come from: the map's pair, or (involution) the 16 bytes at n - 2 - i, swapped
+            uint2 j{n - 2 - i, 0};
+            if (map) j = *reinterpret_cast<const uint2 *>(map + i);
+            const auto moved = [&](const u64 *src) {
+                if (map) return U2{src[j.x], src[j.y]};
+                const U2 v = *reinterpret_cast<const U2 *>(src + j.x);
+                return U2{v.y, v.x};
+            };
+            U2 dw{1, 1};
+            if (dg) dw = *reinterpret_cast<const U2 *>(dg + (size_t)m * n + i);
+            U2 c0{0, 0};
+            if (fold) c0 = moved(c0row);
+            HpAcc acc[2][2];   // carry-save columns (hp_device.h)
+#pragma unroll
+            for (int h = 0; h < 2; h++) { hp_acc_zero(acc[h][0]); hp_acc_zero(acc[h][1]); }
+            for (u32 d = 0; d < nd; d++) {
+                const U2 g0 = ld_nt(key + (((size_t)d * 2 + 0) * E + m) * n + i);
+                const U2 g1 = ld_nt(key + (((size_t)d * 2 + 1) * E + m) * n + i);
+                const u64 kw[2][2] = {{g0.x, g0.y}, {g1.x, g1.y}};
+                const U2 t = moved((d == own) ? c1row : lifted + (((size_t)p * nd + d) * E + m) * n);
+#pragma unroll
+                for (int h = 0; h < 2; h++) hp_mac2(acc[h][0], t.x, kw[h][0], acc[h][1], t.y, kw[h][1]);
+            }
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                U2 v = acc2_montgomery(acc[h][0], acc[h][1], q, mqinv);
+                if (h == 0 && fold) {
+                    v.x += hp_harvey_lazy(c0.x, pm, pmh, q);
+                    v.y += hp_harvey_lazy(c0.y, pm, pmh, q);
+                }
+                hp_mac2(sum[h][0], v.x, dw.x, sum[h][1], v.y, dw.y);
+            }
+        }
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            u64 *dst = out + (((size_t)p * 2 + h) * E + m) * n + i;
+            U2 v = acc2_montgomery(sum[h][0], sum[h][1], q, mqinv);   // the sum * 2^-64 ...
+            v.x = hp_harvey_lazy(v.x, r64, r64h, q);                  // ... * 2^64, below 2q
+            v.y = hp_harvey_lazy(v.y, r64, r64h, q);
+            if (add_prev) {
+                const U2 old = *reinterpret_cast<const U2 *>(dst);
+                v.x = hp_add_lazy(v.x, old.x, two_q);
+                v.y = hp_add_lazy(v.y, old.y, two_q);
+            }
+            st_nt(dst, v);
+        }
+    }
+}
+
+hipError_t hp_launch_hks_inner_lintrans(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 n, u32 P, u32 R, const u64 *lifted,
+                                        const u64 *ct, const HpLinTable &tab, bool add_prev, u64 *acc, hipStream_t stream) {
+    if (P == 0 || R == 0) return hipSuccess;
+    if (R > HP_HOIST_TABLE_MAX) return hipErrorInvalidValue;
+    const u32 chunks = (n + HKS_LT_CHUNK - 1) / HKS_LT_CHUNK;
+    k_hks_inner_lintrans<<<dim3(P * E * chunks, 1, 1), ELEM_THREADS, 0, stream>>>(limbs, hc, P, R, n, chunks, lifted, ct, tab,
+                                                                                add_prev ? 1u : 0u, acc);
+    return hipGetLastError();
+}
+
 // ModDown conversion: Garner digits of the special-prime part once per coefficient, then its exact centred value
 // (x below floor(P/2), x - P from there on; an exact multiple of q_i above the half comes out as q_i, a representative
 // of 0) in every ciphertext modulus

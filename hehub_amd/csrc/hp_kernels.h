@@ -230,6 +230,18 @@ struct HpHoistTable {
 };
 hipError_t hp_launch_hks_inner_hoisted(const HpLimb *limbs, u32 L, u32 E, u32 nd, u32 alpha, u32 n, u32 P, u32 R, const u64 *lifted,
                                        const u64 *pt, u32 pt_pstride, const HpHoistTable &tab, u64 *out, hipStream_t stream);
+// diagonal linear transform in the extended basis (hp_dev_ckks_lintrans_hks): the R rotations of the table weighted and summed
+// inside the thread, ct [P][2][L][n] (digit rows `lifted` of its polynomials 1, as for the hoisted product)
+//   -> acc [P][2][E][n] = sum_r diag_r * ( sum_d map_r(D_d) * key_r[d] )  + on polynomial 0, limbs < L:  (P mod q) * diag_r * map_r(c0)
+// words below 2 * modulus; add_prev: added to the words acc already holds (the launches after the first of a long list).
+// R <= hpi::hks_lintrans_max_rotations (hp_drop.h): the 128-bit accumulators must not wrap
+struct HpLinTable {   // a table of its own: the hoisted kernel's argument block stays as it is
+    const u64 *key[HP_HOIST_TABLE_MAX];
+    const u32 *map[HP_HOIST_TABLE_MAX];
+    const u64 *diag[HP_HOIST_TABLE_MAX];   // [E][n] plain words below 2 * modulus, NTT form; NULL: the constant 1
+};
+hipError_t hp_launch_hks_inner_lintrans(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 n, u32 P, u32 R, const u64 *lifted,
+                                        const u64 *ct, const HpLinTable &tab, bool add_prev, u64 *acc, hipStream_t stream);
 // merged ModDown + rescale (hp_engine.cpp: hks_mult): rem[p2][i] += (P mod q_i) * centre(c_last[p2]) for i < L-1, in the
 // coefficient domain; c_last = strict coefficients modulo q_{L-1} of the relinearised limb L-1
 hipError_t hp_launch_hks_combine(const HpLimb *limbs, const HpHksConsts *hc, u32 L, u32 n, u32 P2, const u64 *clast, u64 *rem,

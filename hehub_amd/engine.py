@@ -461,6 +461,21 @@ class Engine:
                                                           self._ptr(ct), kp, self._ptr(out)))
         return out
 
+    def ckks_lintrans_hks(self, moduli_ext, k: int, alpha: int, ct, keys, steps, diags, conj=None):
+        """sum_r diags[r] * rot_r(ct) for ct [B][2][L][n] with one hybrid key per rotation, the weighted sum formed before ONE ModDown
+        -> [B][2][L][n].  diags[r]: device tensor [L+k][n], NTT form over the extended chain, plain lazy words; None: the constant 1."""
+        B, _, L, n = ct.shape
+        R = len(keys)
+        assert len(steps) == R and len(diags) == R and (conj is None or len(conj) == R)
+        out = self.empty((B, 2, L, n))
+        kp = (capi.P * R)(*[key.data_ptr() for key in keys])
+        dp = (capi.P * R)(*[None if d is None else d.data_ptr() for d in diags])
+        st = (C.c_size_t * R)(*[int(s) for s in steps])
+        cj = (C.c_ubyte * R)(*[1 if c else 0 for c in conj]) if conj is not None else None
+        self._chk(self.lib.hp_dev_ckks_lintrans_hks(self.h, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), B, R, st, cj,
+                                                    self._ptr(ct), kp, dp, self._ptr(out)))
+        return out
+
     def ckks_mult_hks(self, moduli_ext, k: int, alpha: int, ct1, ct2, key, out=None):
         B, _, L, n = ct1.shape
         out = self.empty((B, 2, L - 1, n)) if out is None else out

@@ -512,6 +512,27 @@ int hp_dev_ckks_conjugate_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size
 int hp_dev_ckks_rotate_hoisted_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
                                    size_t batch, size_t rotations, const size_t *steps, const unsigned char *conj,
                                    const uint64_t *d_ct, const uint64_t *const *d_keys, uint64_t *d_out);
+/* Diagonal linear transform, double hoisted: d_out u64[batch][2][L][N] ~ sum_r diag_r * rot_r(ct) -- the diagonal loop of a
+ * matrix-vector product -- with steps, conj and d_keys as for hp_dev_ckks_rotate_hoisted_hks and d_diags a HOST array of
+ * `rotations` device addresses: diagonal r as u64[L+k][N], NTT form over the EXTENDED chain (the caller encodes it modulo the
+ * special primes too), plain lazy words (not Montgomery form); a NULL entry is the constant 1.
+ * Every diagonal word MUST be below 2 * modulus, at either parity level: unlike the other level-B calls this one does not take any
+ * u64 there -- a larger word can wrap the 128-bit sum over the rotations unnoticed, and the residues are then undefined.
+ * The weighted sum is formed in the basis Q*P before ModDown: with D the digit rows of the unrotated c1 and move_r rotation r's
+ * cycle / involution,
+ *     acc[b][h][m] = sum_r diag_r[m] * ( sum_d move_r(D[b][d][m]) * key_r[d][h][m] )        for all L + k moduli m
+ *     out[b][h]    = ModDown(acc[b][h]) + (h == 0) * sum_r diag_r[:L] * move_r(c0[b])        (mod each q_i; words < 2 q_i)
+ * so a call costs ONE digit stage, one accumulate kernel and ONE ModDown per ciphertext whatever `rotations` is (L = 10, k = 4,
+ * alpha = 3, 16 rotations: 84 transforms instead of the hoisted call's 504), its workspace is that of hp_dev_hks_switch, and the
+ * result carries the rounding of one ModDown instead of the sum of R scaled ones.  The contract is on residues, as for every
+ * hybrid call; parity level A follows the context.
+ * HP_EINVAL before anything is enqueued: the limits of hp_dev_hks_switch, rotations == 0, a step >= 2^17 (not a conjugation), a
+ * NULL or misaligned key address, a misaligned diagonal address, d_out overlapping d_ct in any way.  HP_EUNSUPPORTED: moduli so
+ * large (near 2^61 with 16 digits, 2^62 at the latest) that one rotation's products no longer fit the 128-bit accumulators. */
+int hp_dev_ckks_lintrans_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                             size_t batch, size_t rotations, const size_t *steps, const unsigned char *conj,
+                             const uint64_t *d_ct, const uint64_t *const *d_keys, const uint64_t *const *d_diags,
+                             uint64_t *d_out);
 /* ckks::mult_low_level + relinearisation with a hybrid key + rescale by q_{L-1}: out u64[batch][2][L-1][N].
  * For N = 2^11 .. 2^15 ModDown and the rescale share one transform per limb: the residues of hp_dev_hks_switch followed by
  * hp_dev_ckks_rescale, in a lazy representative (< 2q) of their own; HP_HKS_TWO_STEP=1 in the environment at hp_ctx_create
