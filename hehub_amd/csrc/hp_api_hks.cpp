@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <vector>
 
 using namespace hpi;
 
@@ -410,6 +411,143 @@ extern "C" int hp_dev_ckks_lintrans_hks(hp_ctx *ctx, size_t logn, size_t L, size
     }
     if ((rc = hks_pdown(ctx, plan, he->dev, logn, L, k, batch, ks, moduli_ext, yp, rem))) return rc;
     return hks_down(ctx, plan, he, logn, L, k, batch, ks, rem, Addend(), moduli_ext, out);
+}
+
+// Baby-step giant-step form of the diagonal transform: out = sum_g rot_g( sum_i diag_{g,i} * rot_i(ct) ), babies + giants keys for
+// babies * giants diagonals.  The linearity argument above, twice: the baby results stay in the extended basis (no ModDown), every
+// giant's weighted sum is formed there and pays ONE ModDown, and the giants' switches are summed in the extended basis again before
+// the last ModDown.  All giants go through each stage together, as P = batch * (giants that are not the identity) polynomials:
+//   1. hks_digits of c1                                      (batch polynomials)
+//   2. baby rows [b][i][2][E][N], c0 folded in               (k_hks_inner_lintrans<BABY>, one launch per argument table)
+//   3. pre[b][g'][2][E][N] = sum_i diag_{g,i} * baby_i       (k_hks_bsgs_presum; an identity giant's row goes straight into acc)
+//   4. hks_pdown + hks_down of pre -> u[b][g'][2][L][N]      (P polynomials)
+//   5. hks_digits of the u1 rows                             (P polynomials)
+//   6. acc[b][2][E][N] (+)= sum_g' switch_g'(u)              (k_hks_inner_lintrans<GIANT>, one launch per argument table)
+//   7. hks_pdown + hks_down of acc -> out                    (batch polynomials)
+// The workspace and the pass plan are hpi::hks_bsgs_plan's (hp_drop.h): a function of the shape alone.  The first digit rows and the
+// baby rows are dead after stage 3; the digit rows of stage 5 take their place.
+extern "C" int hp_dev_ckks_lintrans_bsgs_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                             size_t batch, size_t babies, const size_t *baby_steps, const unsigned char *baby_conj,
+                                             const uint64_t *const *baby_keys, size_t giants, const size_t *giant_steps,
+                                             const unsigned char *giant_conj, const uint64_t *const *giant_keys,
+                                             const uint64_t *const *diags, const uint64_t *ct, uint64_t *out) {
+    HP_ENTER(ctx);
+    HP_REQUIRE(ctx, moduli_ext, baby_steps, baby_keys, giant_steps, giant_keys, diags, ct, out);
+    HP_ALIGNED(ctx, ct, out);
+    int rc = hks_args_ok(ctx, logn, L, k, alpha, batch);
+    if (rc) return rc;
+    if (babies == 0 || giants == 0) return fail(ctx, HP_EINVAL, "lintrans_bsgs: no baby steps or no giant steps");
+    const auto entries_ok = [&](size_t cnt, const size_t *steps, const unsigned char *conj, const uint64_t *const *keys) {
+        for (size_t r = 0; r < cnt; r++) {
+            const bool cj = conj && conj[r];
+            if (!cj && steps[r] >= ((size_t)1 << 17)) return fail(ctx, HP_EINVAL, "rotation step out of range");
+            if (!keys[r] && (cj || steps[r] != 0)) return fail(ctx, HP_EINVAL, "lintrans_bsgs: a NULL key on an entry that is not the identity");
+            if ((uintptr_t)keys[r] & 15u) return fail(ctx, HP_EINVAL, "lintrans_bsgs: misaligned key");
+        }
+        return (int)HP_OK;
+    };
+    if ((rc = entries_ok(babies, baby_steps, baby_conj, baby_keys)) || (rc = entries_ok(giants, giant_steps, giant_conj, giant_keys))) return rc;
+    for (size_t g = 0; g < giants; g++) {
+        bool any = false;
+        for (size_t i = 0; i < babies; i++) {
+            if ((uintptr_t)diags[g * babies + i] & 15u) return fail(ctx, HP_EINVAL, "lintrans_bsgs: misaligned diagonal");
+            any = any || diags[g * babies + i];
+        }
+        if (!any) return fail(ctx, HP_EINVAL, "lintrans_bsgs: a giant step without a diagonal");
+    }
+    const size_t n = (size_t)1 << logn, E = L + k, nd = (L + alpha - 1) / alpha;
+    {
+        const uintptr_t c0 = (uintptr_t)ct, o0 = (uintptr_t)out, bytes = batch * 2 * L * n * 8;
+        if (o0 < c0 + bytes && c0 < o0 + bytes) return fail(ctx, HP_EINVAL, "lintrans_bsgs: the output overlaps the input");
+    }
+    HksBsgsPlan bp;
+    if (!hks_bsgs_plan(moduli_ext, n, L, k, alpha, batch, babies, giants, bp))
+        return fail(ctx, HP_EUNSUPPORTED, "lintrans_bsgs: moduli too large for the 128-bit accumulators");
+    const Plan *plan;
+    if ((rc = get_plan(ctx, logn, moduli_ext, E, true, &plan))) return rc;
+    const HksEntry *he;
+    if ((rc = get_hks_consts(ctx, moduli_ext, L, k, alpha, &he))) return rc;
+    LevelScope lvl(ctx, plan);   // level A: the digit stages and the drops on the FP64 kernels, as in hp_dev_hks_switch
+    if (lvl.rc) return lvl.rc;
+    if ((rc = ws_reserve(ctx, bp.words * 8))) return rc;
+    std::vector<size_t> keyed;   // the giants that switch, in order: polynomial b * GK + (index here) from stage 3 to stage 6
+    for (size_t g = 0; g < giants; g++)
+        if (giant_keys[g]) keyed.push_back(g);
+    const size_t GK = keyed.size(), rows = 2 * E * n;
+    Carver cv(ctx->ws), late(ctx->ws);   // `late`: stage 5's digit rows, over the first digit rows and the baby rows
+    u64 *lifted;
+    if ((rc = hks_digits(ctx, plan, he->dev, logn, L, k, alpha, batch, ct + L * n, 2 * L, &lifted, cv))) return rc;
+    u64 *baby = cv.take(batch * babies * rows);
+    cv.off = bp.overlay_words * 8;
+    u64 *acc = cv.take(batch * rows), *pre = cv.take(batch * giants * rows), *yp = cv.take(2 * batch * giants * k * n),
+        *rem = cv.take(2 * batch * giants * L * n), *u = cv.take(batch * giants * 2 * L * n);
+    // a table of rotations [r0, r0 + cnt) of a list; a NULL key with a NULL map is the identity (babies only: keyed giants come here)
+    const auto fill = [&](HpLinTable &ht, const size_t *steps, const unsigned char *conj, const uint64_t *const *keys, const size_t *idx,
+                          size_t r0, size_t cnt) {
+        memset(&ht, 0, sizeof(ht));
+        int e = reserve_cycle_perms(ctx, cnt);   // (a miss in a full map cache empties it: not between these)
+        for (size_t r = 0; r < cnt && !e; r++) {
+            const size_t at = idx ? idx[r0 + r] : r0 + r;
+            ht.key[r] = keys[at];
+            if (keys[at] && !(conj && conj[at])) e = get_cycle_perm(ctx, logn, steps[at], &ht.map[r]);
+        }
+        return e;
+    };
+    for (size_t i0 = 0; i0 < babies; i0 += HP_HOIST_TABLE_MAX) {   // stage 2
+        const size_t cnt = std::min<size_t>(HP_HOIST_TABLE_MAX, babies - i0);
+        HpLinTable ht;
+        if ((rc = fill(ht, baby_steps, baby_conj, baby_keys, nullptr, i0, cnt))) return rc;
+        ProfScope ps(ctx, "ks_inner");
+        if ((rc = chk(ctx, hp_launch_hks_bsgs_babies(plan->d_limbs, he->dev, (u32)E, (u32)n, (u32)batch, (u32)cnt, (u32)babies, lifted, ct, ht,
+                                                     baby + i0 * rows, ctx->stream), "hks_bsgs_babies")))
+            return rc;
+    }
+    // stage 3.  A launch holds giants that write DIFFERENT rows: the keyed giants presum_giants at a time into pre, every identity
+    // giant alone into acc (two of them in one launch would race on it)
+    bool acc_written = false;
+    const auto presum = [&](const size_t *gs, size_t gcnt, bool to_acc) {
+        for (size_t i0 = 0; i0 < babies; i0 += bp.baby_pass) {
+            const size_t cnt = std::min(bp.baby_pass, babies - i0);
+            HpPreTable pt;
+            memset(&pt, 0, sizeof(pt));
+            for (size_t c = 0; c < gcnt; c++) {
+                const size_t g = gs[c];
+                for (size_t i = 0; i < cnt; i++) pt.diag[c * cnt + i] = diags[g * babies + i0 + i];
+                pt.dst[c] = to_acc ? acc : pre + (size_t)(gs + c - keyed.data()) * rows;
+            }
+            const bool add = to_acc ? acc_written : i0 != 0;
+            ProfScope ps(ctx, "ks_inner");
+            int e = chk(ctx, hp_launch_hks_bsgs_presum(plan->d_limbs, (u32)E, (u32)n, (u32)batch, (u32)gcnt, (u32)cnt, baby + i0 * rows,
+                                                       babies * rows, pt, to_acc ? rows : GK * rows, add, ctx->stream), "hks_bsgs_presum");
+            if (e) return e;
+            if (to_acc) acc_written = true;
+        }
+        return (int)HP_OK;
+    };
+    for (size_t g = 0; g < giants; g++)
+        if (!giant_keys[g] && (rc = presum(&g, 1, true))) return rc;
+    for (size_t c0 = 0; c0 < GK; c0 += bp.presum_giants)
+        if ((rc = presum(keyed.data() + c0, std::min(bp.presum_giants, GK - c0), false))) return rc;
+    if (GK) {
+        const size_t P = batch * GK;
+        if ((rc = hks_pdown(ctx, plan, he->dev, logn, L, k, P, pre, moduli_ext, yp, rem))) return rc;           // stage 4
+        if ((rc = hks_down(ctx, plan, he, logn, L, k, P, pre, rem, Addend(), moduli_ext, u))) return rc;
+        u64 *lifted2;
+        if ((rc = hks_digits(ctx, plan, he->dev, logn, L, k, alpha, P, u + L * n, 2 * L, &lifted2, late))) return rc;   // stage 5
+        for (size_t c0 = 0; c0 < GK; c0 += bp.giant_pass) {                                                     // stage 6
+            const size_t cnt = std::min(bp.giant_pass, GK - c0);
+            HpLinTable ht;
+            if ((rc = fill(ht, giant_steps, giant_conj, giant_keys, keyed.data(), c0, cnt))) return rc;
+            ProfScope ps(ctx, "ks_inner");
+            if ((rc = chk(ctx, hp_launch_hks_bsgs_giants(plan->d_limbs, he->dev, (u32)E, (u32)n, (u32)batch, (u32)cnt, (u32)GK,
+                                                         lifted2 + c0 * nd * E * n, u + c0 * 2 * L * n, ht, acc_written, acc, ctx->stream),
+                          "hks_bsgs_giants")))
+                return rc;
+            acc_written = true;
+        }
+    }
+    if ((rc = hks_pdown(ctx, plan, he->dev, logn, L, k, batch, acc, moduli_ext, yp, rem))) return rc;           // stage 7
+    return hks_down(ctx, plan, he, logn, L, k, batch, acc, rem, Addend(), moduli_ext, out);
 }
 
 // ckks::mult_low_level + relinearisation with a hybrid key + rescale by the last ciphertext modulus

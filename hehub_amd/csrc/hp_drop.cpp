@@ -154,6 +154,25 @@ size_t hks_lintrans_max_rotations(const u64 *mext, size_t E, size_t nd, size_t t
     return r < table_max ? (size_t)r : table_max;
 }
 
+bool hks_bsgs_plan(const u64 *mext, size_t n, size_t L, size_t k, size_t alpha, size_t batch, size_t babies, size_t giants,
+                   HksBsgsPlan &out) {
+    out = HksBsgsPlan();
+    if (babies == 0 || giants == 0 || alpha == 0) return false;
+    const size_t E = L + k, nd = (L + alpha - 1) / alpha, B = batch, G = giants;
+    const size_t cap = hks_lintrans_max_rotations(mext, E, nd, HP_BSGS_TABLE_MAX);
+    if (cap == 0) return false;
+    const auto pad = [](size_t words) { return ((words * 8 + 255) & ~(size_t)255) / 8; };   // (hp_ctx.h: padded, in words)
+    out.baby_pass = std::min(cap, babies);
+    out.giant_pass = std::min<size_t>(G, HP_BSGS_TABLE_MAX);
+    out.presum_giants = std::min(std::min<size_t>(G, HP_BSGS_GIANT_MAX), (size_t)HP_BSGS_DIAG_MAX / out.baby_pass);
+    const size_t first = pad(B * L * n) + pad(B * nd * E * n) + pad(B * babies * 2 * E * n);
+    const size_t second = pad(B * G * L * n) + pad(B * G * nd * E * n);
+    out.overlay_words = std::max(first, second);
+    out.words = out.overlay_words + pad(B * 2 * E * n) + pad(B * G * 2 * E * n) + pad(2 * B * G * k * n) + pad(2 * B * G * L * n) +
+                pad(B * G * 2 * L * n);
+    return true;
+}
+
 void a_raw_rows(HpDropArgs &da) {
     da.raw_input = 0;
     da.dc.bgv = 0;

@@ -146,6 +146,30 @@ bool hks_limb_consts(const u64 *mext, size_t L, size_t k, HksLimbConsts &out);  
 // products of lazy words, plus the folded c0 term) is below w = 4 nd ceil(q^2 / 2^64) + 3q, which must be a 64-bit word, and a
 // diagonal word below 2q: the largest R with R w 2q < 2^128.  Exact integers.
 size_t hks_lintrans_max_rotations(const u64 *mext, size_t E, size_t nd, size_t table_max);
+// The pass plan and the workspace of hp_dev_ckks_lintrans_bsgs_hks (hp_api_hks.cpp), a function of the shape alone -- never of the
+// steps or of which diagonals are present.  With E = L + k, nd = ceil(L / alpha), pad(w) = w words rounded up to 256 bytes:
+//   baby_pass     babies per pre-sum launch (and per baby-stage launch): hks_lintrans_max_rotations(mext, E, nd, HP_BSGS_TABLE_MAX) --
+//                 the pre-sum multiplies a baby word (the bound of w_r plus the folded word) by a diagonal word below 2q, the flat
+//                 kernel's range argument -- capped by `babies`
+//   giant_pass    giants per accumulate launch: min(giants, HP_BSGS_TABLE_MAX) (their words are summed with weight 1)
+//   presum_giants giants per pre-sum launch: min(giants, HP_BSGS_GIANT_MAX, HP_BSGS_DIAG_MAX / baby_pass) -- the launch's table holds
+//                 HP_BSGS_DIAG_MAX diagonal addresses
+//   words         max( pad(B L n) + pad(B nd E n) + pad(B babies 2 E n),            first digit rows + baby rows, dead after the pre-sum
+//                      pad(B G L n) + pad(B G nd E n) )                            ... where the giants' digit rows then live
+//                 + pad(B 2 E n) + pad(B G 2 E n)                                  acc, pre
+//                 + pad(2 B G k n) + pad(2 B G L n) + pad(B G 2 L n)               yp, rem (both ModDown stages), u
+//                 (B = batch, G = giants: an identity giant leaves its share unused)
+// false: hks_lintrans_max_rotations returns 0 (HP_EUNSUPPORTED), or babies == 0 or giants == 0.
+#define HP_BSGS_TABLE_MAX 32    // == HP_HOIST_TABLE_MAX (hp_kernels.h asserts it)
+#define HP_BSGS_GIANT_MAX 32
+#define HP_BSGS_DIAG_MAX 256
+struct HksBsgsPlan {
+    size_t baby_pass, giant_pass, presum_giants;
+    size_t overlay_words;   // the first term of `words`: where the regions that outlive the pre-sum begin
+    size_t words;
+};
+bool hks_bsgs_plan(const u64 *mext, size_t n, size_t L, size_t k, size_t alpha, size_t batch, size_t babies, size_t giants,
+                   HksBsgsPlan &out);
 // level A: the transform's input rows ARE the remainders -- centring against a threshold out of reach (2^62) does nothing
 void a_raw_rows(HpDropArgs &da);
 // ModDown of the limbs [i0, i0 + cnt): out = (x - NTT(rem)) P^-1 [+ addend]; level B, then that block to level A

@@ -226,13 +226,22 @@ hipError_t hp_launch_hks_inner_hoisted(const HpLimb *limbs, u32 L, u32 E, u32 nd
 // Workgroups: one pair per thread (chunks of 2 * ELEM_THREADS words -- the rotations no longer widen the grid), units = (modulus,
 // ciphertext) numbered by XCD as in the hoisted kernel: the digit rows of a unit are now read R times by the SAME workgroups.
 // Unmeasured for this kernel.  One ciphertext per thread at every batch: two sets of accumulators already leave 4 waves per SIMD.
+// Flavours (hp_dev_ckks_lintrans_bsgs_hks; FLAV is a compile-time branch, the flat flavour's code is what it was):
+//   HKS_LT_GIANT  rotation r reads ITS OWN polynomial p * Rtot + r -- digit rows and the rows (u0, u1) where the flat call has (c0, c1) --
+//                 and there is no diagonal: the sum over the giants of one ciphertext, the words w_r summed with weight 1
+//   HKS_LT_BABY   nothing is summed: the rotations widen the grid as in the hoisted kernel and the word w_r + the folded word goes
+//                 to row set p * Rtot + r as it is (a 64-bit word under the bound above, which is what the pre-sum's range argument
+//                 takes).  A NULL key is the identity: (P mod q) * c_h on the ciphertext moduli, zero on the special primes.
+//                 The rows are read again by the pre-sum: ordinary stores.
 #define HKS_LT_CHUNK (2u * ELEM_THREADS)
+enum { HKS_LT_FLAT = 0, HKS_LT_GIANT = 1, HKS_LT_BABY = 2 };
+template <int FLAV>
 __global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner_lintrans(const HpLimb *__restrict__ limbs, const HpHksConsts *__restrict__ hc,
-                                                                   u32 P, u32 R, u32 n, u32 chunks, const u64 *__restrict__ lifted,
-                                                                   const u64 *__restrict__ ct, HpLinTable tab, u32 add_prev,
-                                                                   u64 *__restrict__ out) {
+                                                                   u32 P, u32 R, u32 Rtot, u32 n, u32 chunks,
+                                                                   const u64 *__restrict__ lifted, const u64 *__restrict__ ct,
+                                                                   HpLinTable tab, u32 add_prev, u64 *__restrict__ out) {
     const u32 L = hc->L, E = hc->E, nd = hc->nd, alpha = hc->alpha;
-    const u32 units = E * P, W = chunks, grouped = (units & ~7u) * W;
+    const u32 units = E * P, W = FLAV == HKS_LT_BABY ? R * chunks : chunks, grouped = (units & ~7u) * W;
     u32 unit, w;
     if (blockIdx.x < grouped) {
         unit = (blockIdx.x / (8 * W)) * 8 + (blockIdx.x & 7u);
@@ -242,21 +251,36 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner_lintrans(const HpLim
         w = (blockIdx.x - grouped) % W;
     }
     const u32 m = unit / P, p = unit % P;
-    const ElemTile tile(ElemTile::At{unit, w}, n, HKS_LT_CHUNK);
+    const ElemTile tile(ElemTile::At{unit, w % chunks}, n, HKS_LT_CHUNK);
+    const u32 r_first = FLAV == HKS_LT_BABY ? w / chunks : 0, r_end = FLAV == HKS_LT_BABY ? r_first + 1 : R;
     const u64 q = limbs[m].q, mqinv = limbs[m].mqinv, two_q = limbs[m].two_q, r64 = limbs[m].r64, r64h = limbs[m].r64h;
     const u32 own = (m < L) ? m / alpha : nd;   // the digit this modulus belongs to (none for the special primes)
     const bool fold = m < L;                    // polynomial 0 of these rows takes the c0 term
     const u64 pm = fold ? hc->p_mod_q[m] : 0, pmh = fold ? hc->p_mod_q_h[m] : 0;
-    const u64 *__restrict__ c0row = ct + ((size_t)p * 2 * L + m) * n;   // a ciphertext is 2 L rows: c0, then c1
-    const u64 *__restrict__ c1row = c0row + (size_t)L * n;
     for (const u32 i : tile.pairs()) {
         HpAcc sum[2][2];   // the outer sum over the rotations
 #pragma unroll
         for (int h = 0; h < 2; h++) { hp_acc_zero(sum[h][0]); hp_acc_zero(sum[h][1]); }
-        for (u32 r = 0; r < R; r++) {
+        for (u32 r = r_first; r < r_end; r++) {
             const u64 *__restrict__ key = tab.key[r];
             const u32 *__restrict__ map = tab.map[r];   // NULL: the involution i -> n - 1 - i
-            const u64 *__restrict__ dg = tab.diag[r];   // NULL: the constant 1
+            const u64 *__restrict__ dg = FLAV == HKS_LT_FLAT ? tab.diag[r] : nullptr;   // NULL: the constant 1
+            const size_t pr = FLAV == HKS_LT_GIANT ? (size_t)p * Rtot + r : p;          // the polynomial rotation r reads
+            const u64 *__restrict__ c0row = ct + (pr * 2 * L + m) * n;   // a ciphertext is 2 L rows: c0, then c1
+            const u64 *__restrict__ c1row = c0row + (size_t)L * n;
+            if (FLAV == HKS_LT_BABY && !key) {   // the identity baby
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    U2 v{0, 0};
+                    if (fold) {
+                        v = *reinterpret_cast<const U2 *>((h ? c1row : c0row) + i);
+                        v.x = hp_harvey_lazy(v.x, pm, pmh, q);
+                        v.y = hp_harvey_lazy(v.y, pm, pmh, q);
+                    }
+                    *reinterpret_cast<U2 *>(out + ((((size_t)p * Rtot + r) * 2 + h) * E + m) * n + i) = v;
+                }
+                continue;
+            }
             // where the two digit words come from: the map's pair, or (involution) the 16 bytes at n - 2 - i, swapped
             uint2 j{n - 2 - i, 0};
             if (map) j = *reinterpret_cast<const uint2 *>(map + i);
@@ -276,7 +300,7 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner_lintrans(const HpLim
                 const U2 g0 = ld_nt(key + (((size_t)d * 2 + 0) * E + m) * n + i);
                 const U2 g1 = ld_nt(key + (((size_t)d * 2 + 1) * E + m) * n + i);
                 const u64 kw[2][2] = {{g0.x, g0.y}, {g1.x, g1.y}};
-                const U2 t = moved((d == own) ? c1row : lifted + (((size_t)p * nd + d) * E + m) * n);
+                const U2 t = moved((d == own) ? c1row : lifted + ((pr * nd + d) * E + m) * n);
 #pragma unroll
                 for (int h = 0; h < 2; h++) hp_mac2(acc[h][0], t.x, kw[h][0], acc[h][1], t.y, kw[h][1]);
             }
@@ -287,9 +311,11 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner_lintrans(const HpLim
                     v.x += hp_harvey_lazy(c0.x, pm, pmh, q);
                     v.y += hp_harvey_lazy(c0.y, pm, pmh, q);
                 }
-                hp_mac2(sum[h][0], v.x, dw.x, sum[h][1], v.y, dw.y);
+                if (FLAV == HKS_LT_BABY) *reinterpret_cast<U2 *>(out + ((((size_t)p * Rtot + r) * 2 + h) * E + m) * n + i) = v;
+                else hp_mac2(sum[h][0], v.x, dw.x, sum[h][1], v.y, dw.y);
             }
         }
+        if (FLAV == HKS_LT_BABY) continue;
 #pragma unroll
         for (int h = 0; h < 2; h++) {
             u64 *dst = out + (((size_t)p * 2 + h) * E + m) * n + i;
@@ -306,14 +332,96 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner_lintrans(const HpLim
     }
 }
 
-hipError_t hp_launch_hks_inner_lintrans(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 n, u32 P, u32 R, const u64 *lifted,
-                                        const u64 *ct, const HpLinTable &tab, bool add_prev, u64 *acc, hipStream_t stream) {
+template <int FLAV>
+static hipError_t hks_lintrans_launch(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 n, u32 P, u32 R, u32 Rtot, const u64 *lifted,
+                                      const u64 *ct, const HpLinTable &tab, bool add_prev, u64 *out, hipStream_t stream) {
     if (P == 0 || R == 0) return hipSuccess;
     if (R > HP_HOIST_TABLE_MAX) return hipErrorInvalidValue;
-    const u32 chunks = (n + HKS_LT_CHUNK - 1) / HKS_LT_CHUNK;
-    k_hks_inner_lintrans<<<dim3(P * E * chunks, 1, 1), ELEM_THREADS, 0, stream>>>(limbs, hc, P, R, n, chunks, lifted, ct, tab,
-                                                                                add_prev ? 1u : 0u, acc);
+    const u32 chunks = (n + HKS_LT_CHUNK - 1) / HKS_LT_CHUNK, W = FLAV == HKS_LT_BABY ? R * chunks : chunks;
+    k_hks_inner_lintrans<FLAV><<<dim3(P * E * W, 1, 1), ELEM_THREADS, 0, stream>>>(limbs, hc, P, R, Rtot, n, chunks, lifted, ct, tab,
+                                                                                 add_prev ? 1u : 0u, out);
     return hipGetLastError();
+}
+hipError_t hp_launch_hks_inner_lintrans(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 n, u32 P, u32 R, const u64 *lifted,
+                                        const u64 *ct, const HpLinTable &tab, bool add_prev, u64 *acc, hipStream_t stream) {
+    return hks_lintrans_launch<HKS_LT_FLAT>(limbs, hc, E, n, P, R, R, lifted, ct, tab, add_prev, acc, stream);
+}
+hipError_t hp_launch_hks_bsgs_babies(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 n, u32 P, u32 R, u32 Rtot, const u64 *lifted,
+                                     const u64 *ct, const HpLinTable &tab, u64 *baby, hipStream_t stream) {
+    return hks_lintrans_launch<HKS_LT_BABY>(limbs, hc, E, n, P, R, Rtot, lifted, ct, tab, false, baby, stream);
+}
+hipError_t hp_launch_hks_bsgs_giants(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 n, u32 P, u32 R, u32 Rtot, const u64 *lifted,
+                                     const u64 *u, const HpLinTable &tab, bool add_prev, u64 *acc, hipStream_t stream) {
+    return hks_lintrans_launch<HKS_LT_GIANT>(limbs, hc, E, n, P, R, Rtot, lifted, u, tab, add_prev, acc, stream);
+}
+
+// Pre-sum of the baby-step giant-step transform: pre_g = sum_i diag_{g,i} * baby_i in the extended basis, the outer sum of the flat
+// kernel with the inner product already done (the baby rows).  A thread owns one pair of words of (b, m) for BOTH halves -- one
+// diagonal load serves h = 0 and h = 1 -- and a tile of GT giants: a baby pair is loaded once per tile, so a baby row is read
+// ceil(giants / GT) times per launch (ordinary cached loads), a diagonal word once per call (non-temporal).  The table is a kernel
+// argument: an absent diagonal is a NULL that the whole wave sees, and costs no load.  The tail is the flat kernel's: one Montgomery
+// reduction of the 128-bit sum, then the Harvey multiplication by 2^64 mod q, below 2q.  Ranges: a baby word is below the flat
+// kernel's bound for w_r plus the folded word, a diagonal word below 2q, `babies` of them per launch (hpi::hks_bsgs_plan).
+// GT = 4: 16 accumulators of 8 VGPRs; the counts are in DESIGN 4.7b (tests/test_bsgs_resources.py prints them).
+// Workgroups: row = ((b * E + m) * tiles + tile), plain numbering -- the tiles of one (b, m) read the same baby rows and are
+// `chunks` workgroups apart.  Unmeasured.
+#define HKS_PRE_GT 4
+template <int GT>
+__global__ void __launch_bounds__(ELEM_THREADS) k_hks_bsgs_presum(const HpLimb *__restrict__ limbs, u32 E, u32 G, u32 Bn, u32 n, u32 chunks,
+                                                                const u64 *__restrict__ baby, size_t baby_pstride, HpPreTable tab,
+                                                                size_t dst_pstride, u32 add_prev) {
+    const u32 tiles = (G + GT - 1) / GT;
+    const ElemTile tile(n, chunks, HKS_LT_CHUNK);
+    const u32 g0 = (tile.row % tiles) * GT, m = (tile.row / tiles) % E, b = tile.row / (tiles * E);
+    const u64 q = limbs[m].q, mqinv = limbs[m].mqinv, two_q = limbs[m].two_q, r64 = limbs[m].r64, r64h = limbs[m].r64h;
+    const u64 *__restrict__ brow = baby + (size_t)b * baby_pstride + (size_t)m * n;   // baby i, half h: + (i * 2 + h) * E * n
+    for (const u32 i : tile.pairs()) {
+        HpAcc sum[GT][2][2];
+#pragma unroll
+        for (int c = 0; c < GT; c++)
+#pragma unroll
+            for (int h = 0; h < 2; h++) { hp_acc_zero(sum[c][h][0]); hp_acc_zero(sum[c][h][1]); }
+        for (u32 j = 0; j < Bn; j++) {
+            const U2 v0 = *reinterpret_cast<const U2 *>(brow + ((size_t)j * 2 + 0) * E * n + i);
+            const U2 v1 = *reinterpret_cast<const U2 *>(brow + ((size_t)j * 2 + 1) * E * n + i);
+#pragma unroll
+            for (int c = 0; c < GT; c++) {
+                const u64 *__restrict__ dg = g0 + c < G ? tab.diag[(g0 + c) * Bn + j] : nullptr;
+                if (dg) {
+                    const U2 dw = ld_nt(dg + (size_t)m * n + i);
+                    hp_mac2(sum[c][0][0], v0.x, dw.x, sum[c][0][1], v0.y, dw.y);
+                    hp_mac2(sum[c][1][0], v1.x, dw.x, sum[c][1][1], v1.y, dw.y);
+                }
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < GT; c++) {
+            if (g0 + c < G) {
+#pragma unroll
+                for (int h = 0; h < 2; h++) {
+                    u64 *dst = tab.dst[g0 + c] + (size_t)b * dst_pstride + ((size_t)h * E + m) * n + i;
+                    U2 v = acc2_montgomery(sum[c][h][0], sum[c][h][1], q, mqinv);   // the sum * 2^-64 ...
+                    v.x = hp_harvey_lazy(v.x, r64, r64h, q);                        // ... * 2^64, below 2q
+                    v.y = hp_harvey_lazy(v.y, r64, r64h, q);
+                    if (add_prev) {
+                        const U2 old = *reinterpret_cast<const U2 *>(dst);
+                        v.x = hp_add_lazy(v.x, old.x, two_q);
+                        v.y = hp_add_lazy(v.y, old.y, two_q);
+                    }
+                    st_nt(dst, v);
+                }
+            }
+        }
+    }
+}
+
+hipError_t hp_launch_hks_bsgs_presum(const HpLimb *limbs, u32 E, u32 n, u32 P, u32 giants, u32 babies, const u64 *baby, size_t baby_pstride,
+                                     const HpPreTable &tab, size_t dst_pstride, bool add_prev, hipStream_t stream) {
+    if (P == 0 || giants == 0 || babies == 0) return hipSuccess;
+    if (giants > HP_BSGS_GIANT_MAX || giants * babies > HP_BSGS_DIAG_MAX) return hipErrorInvalidValue;
+    const u32 tiles = (giants + HKS_PRE_GT - 1) / HKS_PRE_GT;
+    return elem_launch_cw(k_hks_bsgs_presum<HKS_PRE_GT>, HKS_LT_CHUNK, P * E * tiles, n, stream, limbs, E, giants, babies, n, ElemChunks{},
+                          baby, baby_pstride, tab, dst_pstride, add_prev ? 1u : 0u);
 }
 
 // ModDown conversion: Garner digits of the special-prime part once per coefficient, then its exact centred value

@@ -242,6 +242,27 @@ struct HpLinTable {   // a table of its own: the hoisted kernel's argument block
 };
 hipError_t hp_launch_hks_inner_lintrans(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 n, u32 P, u32 R, const u64 *lifted,
                                         const u64 *ct, const HpLinTable &tab, bool add_prev, u64 *acc, hipStream_t stream);
+// Baby-step giant-step transform (hp_dev_ckks_lintrans_bsgs_hks): two more flavours of the accumulate kernel, and the pre-sum.
+//   babies: rotation r of the table -> its own row set, nothing summed: baby [P][Rtot][2][E][n] (the launch writes the R sets from
+//           `baby` on) = sum_d map_r(D_d) * key_r[d]  + on polynomial 0, limbs < L: (P mod q) * map_r(c0); a NULL key: the identity,
+//           (P mod q) * c_h on the limbs < L and zero on the special primes.  Words: the bound of w_r plus the folded word (hp_drop.h)
+//   giants: the flat call's sum with every rotation reading ITS OWN polynomial -- digit rows `lifted` and rows u of polynomial
+//           p * Rtot + r, u [P][Rtot][2][L][n] -- and no diagonal -> acc [P][2][E][n], words below 2 * modulus, add_prev as above
+static_assert(HP_BSGS_TABLE_MAX == HP_HOIST_TABLE_MAX, "the plan of hp_drop.h counts in argument tables");
+hipError_t hp_launch_hks_bsgs_babies(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 n, u32 P, u32 R, u32 Rtot, const u64 *lifted,
+                                     const u64 *ct, const HpLinTable &tab, u64 *baby, hipStream_t stream);
+hipError_t hp_launch_hks_bsgs_giants(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 n, u32 P, u32 R, u32 Rtot, const u64 *lifted,
+                                     const u64 *u, const HpLinTable &tab, bool add_prev, u64 *acc, hipStream_t stream);
+// pre-sum: dst[g][b][h][m] = sum_i diag[g * babies + i][m] * baby[b][i][h][m] for the `giants` giants and `babies` babies of the
+// table (baby row set i of ciphertext b at baby + b * baby_pstride + i * 2 E n; giant g's rows of ciphertext b at
+// dst[g] + b * dst_pstride), words below 2 * modulus; a NULL diagonal: the term is absent; add_prev: added to what dst holds.
+// babies <= hpi::hks_bsgs_plan's baby_pass (the 128-bit sums), giants * babies <= HP_BSGS_DIAG_MAX, giants <= HP_BSGS_GIANT_MAX
+struct HpPreTable {
+    const u64 *diag[HP_BSGS_DIAG_MAX];   // [E][n] plain words below 2 * modulus, NTT form
+    u64 *dst[HP_BSGS_GIANT_MAX];
+};
+hipError_t hp_launch_hks_bsgs_presum(const HpLimb *limbs, u32 E, u32 n, u32 P, u32 giants, u32 babies, const u64 *baby, size_t baby_pstride,
+                                     const HpPreTable &tab, size_t dst_pstride, bool add_prev, hipStream_t stream);
 // merged ModDown + rescale (hp_engine.cpp: hks_mult): rem[p2][i] += (P mod q_i) * centre(c_last[p2]) for i < L-1, in the
 // coefficient domain; c_last = strict coefficients modulo q_{L-1} of the relinearised limb L-1
 hipError_t hp_launch_hks_combine(const HpLimb *limbs, const HpHksConsts *hc, u32 L, u32 n, u32 P2, const u64 *clast, u64 *rem,

@@ -476,6 +476,31 @@ class Engine:
                                                     self._ptr(ct), kp, dp, self._ptr(out)))
         return out
 
+    def ckks_lintrans_bsgs_hks(self, moduli_ext, k: int, alpha: int, ct, baby_keys, baby_steps, giant_keys, giant_steps, diags,
+                               baby_conj=None, giant_conj=None):
+        """sum_g rot_g( sum_i diags[g][i] * rot_i(ct) ) for ct [B][2][L][n]: len(baby_keys) + len(giant_keys) hybrid keys for their
+        product of diagonals -> [B][2][L][n].  diags[g][i]: device tensor [L+k][n], NTT form over the extended chain, plain lazy words,
+        NOT rotated by the call (pass rot_g^-1 of the matrix's diagonal g + i); None: the term is ABSENT (in ckks_lintrans_hks None is
+        the constant 1).  A key may be None where the step is 0 and the entry no conjugation: the identity, no key switch."""
+        B, _, L, n = ct.shape
+        nb, ng = len(baby_keys), len(giant_keys)
+        assert len(baby_steps) == nb and len(giant_steps) == ng and len(diags) == ng and all(len(row) == nb for row in diags)
+        assert (baby_conj is None or len(baby_conj) == nb) and (giant_conj is None or len(giant_conj) == ng)
+        out = self.empty((B, 2, L, n))
+
+        def table(keys, steps, conj):
+            cnt = len(keys)
+            return ((C.c_size_t * cnt)(*[int(s) for s in steps]),
+                    (C.c_ubyte * cnt)(*[1 if c else 0 for c in conj]) if conj is not None else None,
+                    (capi.P * cnt)(*[None if key is None else key.data_ptr() for key in keys]))
+
+        bs, bc, bk = table(baby_keys, baby_steps, baby_conj)
+        gs, gc, gk = table(giant_keys, giant_steps, giant_conj)
+        dp = (capi.P * (ng * nb))(*[None if d is None else d.data_ptr() for row in diags for d in row])
+        self._chk(self.lib.hp_dev_ckks_lintrans_bsgs_hks(self.h, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), B, nb, bs, bc, bk,
+                                                         ng, gs, gc, gk, dp, self._ptr(ct), self._ptr(out)))
+        return out
+
     def ckks_mult_hks(self, moduli_ext, k: int, alpha: int, ct1, ct2, key, out=None):
         B, _, L, n = ct1.shape
         out = self.empty((B, 2, L - 1, n)) if out is None else out

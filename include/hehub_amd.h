@@ -533,6 +533,40 @@ int hp_dev_ckks_lintrans_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_
                              size_t batch, size_t rotations, const size_t *steps, const unsigned char *conj,
                              const uint64_t *d_ct, const uint64_t *const *d_keys, const uint64_t *const *d_diags,
                              uint64_t *d_out);
+/* Diagonal linear transform, baby-step giant-step: with every rotation r of a matrix written r = g + i over `babies` baby steps i
+ * and `giants` giant steps g,
+ *     d_out u64[batch][2][L][N] ~ sum_g rot_g( sum_i diag_{g,i} * rot_i(ct) )
+ * with babies + giants hybrid keys where hp_dev_ckks_lintrans_hks needs babies * giants (16 x 16 diagonals at N = 32768, L = 10, k = 4,
+ * alpha = 3: 32 keys of 29.4 MB instead of 256, 7.5 GB).  baby_steps / baby_conj / d_baby_keys and giant_steps / giant_conj /
+ * d_giant_keys are HOST arrays as for hp_dev_ckks_rotate_hoisted_hks (conj may be NULL), the keys u64[dnum][2][L+k][N].
+ * d_diags is a HOST array of giants * babies device addresses, entry g * babies + i being diag_{g,i} as u64[L+k][N]: NTT form over the
+ * EXTENDED chain, plain lazy words, every word BELOW 2 * modulus at either parity level -- the precondition of
+ * hp_dev_ckks_lintrans_hks, for its reason: a larger word can wrap a 128-bit sum unnoticed and the residues are then undefined.
+ * !! A NULL diagonal means the term (g, i) is ABSENT.  In hp_dev_ckks_lintrans_hks a NULL diagonal is the constant 1.  The two calls
+ * !! differ here on purpose: real matrices are sparse in (g, i).
+ * !! The call does NOT rotate the diagonals.  To apply the matrix with diagonals diag_r the caller passes
+ * !! diag_{g,i} = rot_g^-1(diag_{g+i}): the outer rotation by g then moves the weight back to where diag_{g+i} has it.
+ * A NULL key is allowed exactly on an entry with step 0 that is not a conjugation: that entry is the identity and pays no key switch,
+ * baby or giant alike.  A step-0 entry WITH a key is switched like any other.
+ * The contract is on residues, every output word below 2 q_i.  With D(x) the digit rows of polynomial x, move_s the cycle /
+ * involution of entry s and unmont = 2^-64 (the keys are in Montgomery form), for every one of the L + k moduli m:
+ *     baby_i[h][m] = unmont * sum_d move_i(D(c1)[d][m]) * key_i[d][h][m]  + (h == 0, m < L) * (P mod q_m) * move_i(c0[m])
+ *                    (identity baby: (m < L) * (P mod q_m) * c_h[m], zero on the special primes)
+ *     pre_g[h][m]  = sum_i diag_{g,i}[m] * baby_i[h][m]                                          (absent terms skipped)
+ *     identity giant:  acc[h][m] += pre_g[h][m]                                                  (no ModDown, no digits, no key)
+ *     other giants:    (u0, u1) = ModDown(pre_g);
+ *                      acc[h][m] += unmont * sum_d move_g(D(u1)[d][m]) * key_g[d][h][m]  + (h == 0, m < L) * (P mod q_m) * move_g(u0[m])
+ *     out[h]       = ModDown(acc[h])
+ * The baby results stay in the basis Q*P, each keyed giant pays one ModDown and one digit stage, and all of them go through every stage
+ * together: the launch count does not grow with `giants` (beyond one argument table of 32 entries per launch).  The workspace depends
+ * on (N, L, k, alpha, batch, babies, giants) alone.  Parity level A follows the context.
+ * HP_EINVAL before anything is enqueued: the limits of hp_dev_hks_switch, babies == 0 or giants == 0, a step >= 2^17 (not a
+ * conjugation), a NULL key on an entry that is not the identity, a misaligned key or diagonal address, a giant step all of whose
+ * diagonals are NULL, d_out overlapping d_ct in any way.  HP_EUNSUPPORTED: moduli as large as hp_dev_ckks_lintrans_hks refuses. */
+int hp_dev_ckks_lintrans_bsgs_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t batch,
+                                  size_t babies, const size_t *baby_steps, const unsigned char *baby_conj, const uint64_t *const *d_baby_keys,
+                                  size_t giants, const size_t *giant_steps, const unsigned char *giant_conj, const uint64_t *const *d_giant_keys,
+                                  const uint64_t *const *d_diags, const uint64_t *d_ct, uint64_t *d_out);
 /* ckks::mult_low_level + relinearisation with a hybrid key + rescale by q_{L-1}: out u64[batch][2][L-1][N].
  * For N = 2^11 .. 2^15 ModDown and the rescale share one transform per limb: the residues of hp_dev_hks_switch followed by
  * hp_dev_ckks_rescale, in a lazy representative (< 2q) of their own; HP_HKS_TWO_STEP=1 in the environment at hp_ctx_create
