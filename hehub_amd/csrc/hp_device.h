@@ -316,6 +316,16 @@ HP_DEV u64 hp_sub_lazy(u64 a, u64 b, u64 two_q) {
     return v - ((v >= two_q) ? two_q : 0);
 }
 
+// A lazy transform word brought below 2q, unchanged where it already is.  hehub's fold (ntt.cpp:171-175) leaves words below 2q only
+// where the modulus sits near its power of two; far below it (fix = 0, large 2^k - q) they reach hp::lazy_fold_bound's word_end,
+// under 16q for every modulus and degree the transforms accept, and hehub's lazy subtraction (which takes its operand below 2q) then
+// wraps.  For the engine's OWN pipelines (the hybrid ModDown); hehub's pipelines keep hehub's words, wrapped ones included.
+HP_DEV u64 hp_lazy_below_2q(u64 x, u64 two_q) {
+    x -= (x >= (two_q << 2)) ? (two_q << 2) : 0;
+    x -= (x >= (two_q << 1)) ? (two_q << 1) : 0;
+    return x - ((x >= two_q) ? two_q : 0);
+}
+
 // HP_PACK48: row format of the digit workspace for output moduli whose words are provably below 2^48 (internal to the engine:
 // written by the digit-spread transform, read by the key-switch inner product; 6 instead of 8 bytes per word cross HBM in both
 // directions).  A row keeps its 8N-byte slot: [u32 lo[N]] [u16 hi[N]] [2N bytes unused]; word i = lo[i] | (u64)hi[i] << 32.

@@ -223,6 +223,15 @@ hipError_t hp_launch_hks_inner_hoisted(const HpLimb *limbs, u32 L, u32 E, u32 nd
 // Ranges: w_r + the folded word < 4 nd ceil(q^2 / 2^64) + 3q, times a diagonal word < 2q, summed over R: the host keeps that below
 // 2^128 (hpi::hks_lintrans_max_rotations, hp_drop.h: 32 rotations for every modulus below 2^59).  A diagonal word of 2q or more can
 // make the sum wrap unnoticed: the residues are then undefined.
+// That bound for w_r takes every digit word below 2q.  The caller's own rows are; the lifted rows at level B are hehub's lazy
+// transform words, which exceed 2q where the modulus sits far below its power of two (kb = round(log2 q), fix = 0, large
+// 2^kb - q: hp::lazy_fold_bound's word_end).  Measured on a chain of 58- and 59-bit moduli with 16 digits and 32 rotations
+// (tests/test_hks_edges.py): digit words up to 4.24 q at the 58-bit moduli near 1.6 * 2^58 (N = 1024), the digit sum up to 2^123.97,
+// w_r + the folded word up to 2^60.85 -- still under the bound, 2^61.32 there, which is taken at the LARGEST modulus of the chain
+// while only moduli a good way below a power of two have such rows -- and the outer sum up to 2^125.50.  With lazy_fold_bound's
+// largest word for any modulus the transforms accept (log_modulus <= 59, N <= 65536: under 11 q at q = 2^58.5) the same arithmetic
+// gives 2^125.4, 2^61.9 and 2^126.4: both sums fit 128 bits and the word fits 64 at every supported modulus, so the host formula
+// stands although its premise does not.
 // Workgroups: one pair per thread (chunks of 2 * ELEM_THREADS words -- the rotations no longer widen the grid), units = (modulus,
 // ciphertext) numbered by XCD as in the hoisted kernel: the digit rows of a unit are now read R times by the SAME workgroups.
 // Unmeasured for this kernel.  One ciphertext per thread at every batch: two sets of accumulators already leave 4 waves per SIMD.
@@ -499,6 +508,7 @@ hipError_t hp_launch_hks_combine(const HpLimb *limbs, const HpHksConsts *hc, u32
 }
 
 // ModDown epilogue: out[p2][i] = ((x[p2][i] - rem[p2][i]) * P^-1 mod q_i) [+ addend]; x rows have E limbs, rem / out rows L
+// (rem: the lazy transform of the remainders, brought below 2q first -- hp_lazy_below_2q, hp_device.h: exact at every modulus)
 __global__ void __launch_bounds__(ELEM_THREADS) k_hks_down_fin(const HpLimb *__restrict__ limbs, const HpHksConsts *__restrict__ hc,
                                                              u32 n, u32 chunks, const u64 *__restrict__ x,
                                                              const u64 *__restrict__ rem, const u64 *__restrict__ addend,
@@ -513,7 +523,7 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_down_fin(const HpLimb *__r
     const u64 *as = drop_addend_row(addend, add_poly_stride, add_ct_stride, add_mask, p2, k, n);
     u64 *os = out + (size_t)tile.row * n;
     for (const u32 i : tile.words()) {
-        u64 v = hp_sub_lazy(xs[i], rs[i], two_q);
+        u64 v = hp_sub_lazy(xs[i], hp_lazy_below_2q(rs[i], two_q), two_q);   // (rs: a lazy transform word, not always below 2q)
         v = hp_harvey_lazy(v, hc->pinv[k], hc->pinv_h[k], q);
         if (as) v = hp_add_lazy(v, as[i], two_q);
         os[i] = v;

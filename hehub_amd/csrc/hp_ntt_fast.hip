@@ -205,6 +205,14 @@ HP_DEV void ntt_fwd_body(const HpNttJob &job, const HpDropArgs *da) {
 #pragma unroll
         for (int r = 0; r < 32; ++r) x[r] = hp_shift_fold(x[r], q, k, fix);
     }
+    if constexpr (DROP && FLAV == 0) {
+        // hybrid ModDown (raw rows: the engine's own pipeline, no hehub words to follow): the epilogue's lazy subtraction takes
+        // NTT(rem) below 2q, which the fold alone does not give at every modulus (hp_lazy_below_2q, hp_device.h)
+        if (da->raw_input) {
+#pragma unroll
+            for (int r = 0; r < 32; ++r) x[r] = hp_lazy_below_2q(x[r], two_q);
+        }
+    }
     TRACE_MARK();   // 7: fold done
     exchange<LOGN, LAY_C, LAY_S, false>(x, lds, ad);
     TRACE_MARK();   // 8

@@ -188,8 +188,8 @@ def test_both_entries_the_identity_is_the_product_with_the_diagonal(eng, orc):
 
 
 # ---- (b) one identity giant: the flat call ----------------------------------------------------------------------------------------
-def flat_case(eng, logn, L, k, alpha, seed=7200):
-    mext = P.P40[:L] + P.P50[:k]
+def flat_case(eng, logn, L, k, alpha, seed=7200, mext=None):
+    mext = mext or P.P40[:L] + P.P50[:k]
     n = 1 << logn
     rng = SplitMix(seed + logn)
     steps, conj = [1, 0, 5], [False, True, False]

@@ -14,7 +14,7 @@ import pytest
 
 import params as P
 from oracle.pyoracle import SplitMix
-from test_hks import centred_error, crt, digits_of, keygen
+from test_hks import below_2q, centred_error, crt, digits_of, keygen
 
 pytestmark = pytest.mark.gpu
 U = np.uint64
@@ -70,7 +70,7 @@ def model_rest(orc, logn, mext, L, k, D, key):
         for i_q in range(L):
             q = mext[i_q]
             rem[i_q] = orc.ntt(logn, q, np.array([(y % q) if y < Pprod // 2 else q - ((Pprod - y) % q) for y in ys], dtype=U))
-        diff = orc.poly_sub(mext[:L], np.ascontiguousarray(ks[h, :L]), rem)
+        diff = orc.poly_sub(mext[:L], np.ascontiguousarray(ks[h, :L]), below_2q(rem, mext[:L]))
         out[h] = orc.poly_rns_scalar_mul(mext[:L], diff, [pow(Pprod % q, -1, q) for q in mext[:L]])
     return out
 
@@ -142,8 +142,8 @@ def test_hoisted_matches_the_exact_model(eng, orc, logn, L, k, alpha, B, R):
 
 
 # ---- (b) step 0 is the plain switch ---------------------------------------------------------------------------------------------
-def step0_case(eng, logn, L, k, alpha, seed=5200):
-    mext = P.P40[:L] + P.P50[:k]
+def step0_case(eng, logn, L, k, alpha, seed=5200, mext=None):
+    mext = mext or P.P40[:L] + P.P50[:k]
     n = 1 << logn
     rng = SplitMix(seed + logn)
     ct = rng.poly((2, 2, L, n), mext[:L])

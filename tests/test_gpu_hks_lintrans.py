@@ -112,8 +112,8 @@ def test_lintrans_matches_the_exact_model(eng, orc, logn, L, k, alpha, B, R):
 
 
 # ---- (b) one rotation without a diagonal is the hoisted rotation ---------------------------------------------------------------------
-def single_case(eng, logn, L, k, alpha, seed=6200):
-    mext = P.P40[:L] + P.P50[:k]
+def single_case(eng, logn, L, k, alpha, seed=6200, mext=None):
+    mext = mext or P.P40[:L] + P.P50[:k]
     n = 1 << logn
     rng = SplitMix(seed + logn)
     ct = rng.poly((2, 2, L, n), mext[:L])

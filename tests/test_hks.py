@@ -35,6 +35,17 @@ def crt(residues, moduli):
     return x % Q, Q
 
 
+def below_2q(rows, moduli):
+    """lazy transform words [L][n] brought below 2q the way the ModDown kernels do it (hp_lazy_below_2q, hp_device.h): minus 8q, 4q, 2q
+    where that fits -- nothing where the word already is below 2q, which is everywhere but at moduli far below their power of two,
+    where hehub's fold leaves words of up to 16q and hehub's lazy subtraction would wrap"""
+    rows = rows.copy()
+    for j, q in enumerate(moduli):
+        for s in (8, 4, 2):
+            rows[j] -= np.where(rows[j] >= U(s * q), U(s * q), U(0))
+    return rows
+
+
 def digits_of(L, alpha):
     return [list(range(d * alpha, min((d + 1) * alpha, L))) for d in range((L + alpha - 1) // alpha)]
 
@@ -69,7 +80,7 @@ def model_switch(orc, logn, mext, L, k, alpha, pt, key):
             q = mext[i_q]
             vals = [(y % q) if y < Pm // 2 else q - ((Pm - y) % q) for (y, Pm) in Ys]
             rem[i_q] = orc.ntt(logn, q, np.array(vals, dtype=U))
-        diff = orc.poly_sub(mext[:L], np.ascontiguousarray(ks[h, :L]), rem)
+        diff = orc.poly_sub(mext[:L], np.ascontiguousarray(ks[h, :L]), below_2q(rem, mext[:L]))
         Pprod = 1
         for p in pm:
             Pprod *= p

@@ -1,7 +1,10 @@
 """hpi::hks_lintrans_max_rotations (hp_drop.cpp): how many rotations one launch of k_hks_inner_lintrans may sum before its 128-bit
-accumulators could wrap.  Every modulus of the GPU tests is below 2^51, where the answer is the whole table; the smaller tables and the
+accumulators could wrap.  Every modulus the transforms accept is below 2^59.5, where the answer is the whole table
+(tests/test_gpu_hks_moduli.py runs it at 58 and 59 bits, tests/test_hks_edges.py has the sums); the smaller tables and the
 refusal start near 2^60, which only this test reaches (CPU tier, through tests/cpp/lintrans_shim.cpp, built with g++).  Checked against
-the documented formula in Python integers AND against the property it exists for, with the largest words the kernel can meet."""
+the documented formula in Python integers AND against the property it exists for, with the largest words of the formula's premise
+(digit words below 2q; the lifted rows at level B can exceed that -- tests/test_hks_edges.py measures what they reach and that the
+sums fit all the same)."""
 import ctypes as C
 import os
 import subprocess
