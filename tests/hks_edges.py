@@ -9,11 +9,11 @@ of k_hks_inner_lintrans / k_hks_bsgs_presum come nearest to wrapping.
 Range arithmetic: `sums` recomputes with Python integers what one launch of those kernels accumulates -- the digit sum of every
 rotation, the word it reduces to (plus the folded c0 word), the sum over the rotations weighted by the diagonals -- from the words the
 device really reads at level B: the caller's own words inside a digit, the oracle's lazy transform of the lifted value elsewhere
-(test_gpu_hks_hoisted.model_digits)."""
+(hks_model.model_digits)."""
 import numpy as np
 
 import moduli as M
-from test_gpu_hks_hoisted import model_digits, move, rotations_of
+from hks_model import below_2q, crt, model_digits, move, random_diagonal, rotations_of
 
 U = np.uint64
 M64 = (1 << 64) - 1
@@ -207,7 +207,7 @@ def report(name, worst, mext, nd, R):
 
 # ---- the flat transform at a spread of coefficients ------------------------------------------------------------------------------
 def sampled_lintrans(orc, logn, mext, L, k, alpha, ct, keys, steps, conj, diags, sel, D=None):
-    """test_gpu_hks_lintrans.model_lintrans at the coefficients `sel` of every output row: the canonical residues [2][L][len(sel)].
+    """hks_model.model_lintrans at the coefficients `sel` of every output row: the canonical residues [2][L][len(sel)].
     A None key is an identity term diag * (c0, c1) and the diagonal "absent" no term: the BSGS call with identity giants only.
     ModDown needs the special-prime rows of the accumulator whole (their inverse transform mixes all coefficients); the ciphertext
     moduli's rows only where they are compared.  With sel = range(n) this is model_lintrans (tests/test_hks_edges.py holds it to that)."""
@@ -241,8 +241,6 @@ def sampled_lintrans(orc, logn, mext, L, k, alpha, ct, keys, steps, conj, diags,
     # ModDown word for word as model_rest does it (the accumulator handed through its inner product with the unit "key", hehub's lazy
     # subtraction of the transformed remainder, * P^-1): the representatives matter where the remainder's lazy transform words exceed
     # 2q -- at high_mid moduli hehub's subtraction then wraps, and what comes out depends on the word it is subtracted from
-    from test_hks import below_2q, crt
-
     def handed(a, q):
         x = a * ((1 << 64) % q)
         return orc.montgomery_128_lazy(q, np.stack([(x & M64).astype(U), (x >> 64).astype(U)], axis=1))
@@ -275,8 +273,6 @@ def _pools(rng, fill, n, nd, mext, L):
       max    every word of everything 2q - 1
       edge   ciphertext rows cycled over the kinds (the lifted digits then vary), every key and diagonal word 2q - 1: the largest sums
              real digit rows give"""
-    from test_gpu_hks_lintrans import random_diagonal
-
     E, q = len(mext), mext[:L]
     if fill == "lazy":
         return (lambda B: M.lazy_rows(rng, (B, 2, L, n), q), [lazy_uniform(rng, (nd, 2, E, n), mext) for _ in range(3)],

@@ -120,8 +120,8 @@ def test_many_to_one_base_transform_on_the_crt_branch(eng, orc, L):
 @pytest.mark.parametrize("alpha", [1, 3])
 def test_hybrid_modup_and_moddown_dispatch(eng, orc, alpha):
     """n = 8, L = 3, alpha limbs per digit and alpha special primes: k_hks_modup<alpha> and k_hks_moddown<alpha> against the
-    exact integer model of tests/test_hks.py"""
-    from test_hks import model_switch
+    exact integer model of tests/hks_model.py"""
+    from hks_model import model_switch
 
     logn, L, k = 3, 3, alpha
     mext = P.P40[:L] + P.P50[:k]

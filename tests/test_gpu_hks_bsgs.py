@@ -7,7 +7,7 @@ The contract is on residues (include/hehub_amd.h has it line by line): with D(x)
     identity giant: acc += pre_g;   others: (u0, u1) = ModDown(pre_g), acc += switch_g(u0, u1) in the extended basis
     out[h]       = ModDown(acc[h]),  every word below 2 q_i
 Pinned
-  (a) by that model written with Python integers (ModDown is test_gpu_hks_hoisted.model_rest's with the unit "key");
+  (a) by that model written with Python integers (hks_model.model_bsgs; ModDown is hks_model.model_rest's with the unit "key");
   (b) against hp_dev_ckks_lintrans_hks where one identity giant makes the two the same sum;
   (c) against hp_dev_ckks_lintrans_hks on (diag * c0, diag * c1) for one identity baby and one keyed giant: the giant path alone;
   (d) by decryption with keys generated here, for the device's words and for the model's;
@@ -19,10 +19,9 @@ import numpy as np
 import pytest
 
 import params as P
+from hks_model import (centred_error, chain, decryption_setup, dev, flat_case, model_bsgs, move, random_diagonal, residues_match,
+                       rotations_of)
 from oracle.pyoracle import SplitMix
-from test_gpu_hks_hoisted import chain, decryption_setup, model_digits, model_rest, move, rotations_of
-from test_gpu_hks_lintrans import model_lintrans, random_diagonal  # noqa: F401  (model_lintrans: the flat call's model, for reference)
-from test_hks import centred_error
 
 pytestmark = pytest.mark.gpu
 U = np.uint64
@@ -37,82 +36,7 @@ def eng():
     e.close()
 
 
-# ---- the model -----------------------------------------------------------------------------------------------------------------
-def mod_down(orc, logn, mext, L, k, acc):
-    """acc [2][E] rows of Python integers -> ModDown, canonical residues [2][L][n] (dtype object): model_rest with the unit "key"
-    (2^64 mod q on the diagonal), whose inner product hands the accumulator through unchanged"""
-    n, E = 1 << logn, L + k
-    A = np.array(acc, dtype=object).astype(U)
-    unit = np.zeros((2, 2, E, n), dtype=U)
-    for m in range(E):
-        unit[0, 0, m, :] = unit[1, 1, m, :] = (1 << 64) % mext[m]
-    out = model_rest(orc, logn, mext, L, k, A, unit).astype(object)
-    for m in range(L):
-        out[:, m] %= mext[m]
-    return out
-
-
-def model_switch_ext(orc, logn, mext, L, k, alpha, ct, key, step, cj, D=None):
-    """one rotation's word set in the extended basis, [2][E] rows of Python integers: the contract's baby_i (and the giants' addend).
-    D: the digit rows of ct[1], where the caller already has them"""
-    n, E = 1 << logn, L + k
-    Pprod = 1
-    for p in mext[L:]:
-        Pprod *= p
-    if key is None:
-        return [[(Pprod % mext[m]) * ct[h][m].astype(object) % mext[m] if m < L else np.zeros(n, dtype=object) for m in range(E)]
-                for h in range(2)]
-    if D is None:
-        D = model_digits(orc, logn, mext, L, k, alpha, np.ascontiguousarray(ct[1]))
-    Dm = np.stack([move(orc, D[d], step, cj) for d in range(D.shape[0])]).astype(object)
-    c0m = move(orc, ct[0], step, cj).astype(object)
-    Ko = key.astype(object)
-    rows = [[None] * E for _ in range(2)]
-    for m in range(E):
-        q = mext[m]
-        unmont = pow(1 << 64, -1, q)
-        for h in range(2):
-            w = sum(Dm[d, m] * Ko[d, h, m] for d in range(D.shape[0])) * unmont % q
-            if h == 0 and m < L:
-                w = (w + (Pprod % q) * c0m[m]) % q
-            rows[h][m] = w
-    return rows
-
-
-def model_bsgs(orc, logn, mext, L, k, alpha, ct, bkeys, bsteps, bconj, gkeys, gsteps, gconj, diags):
-    """ct [2][L][n]; keys [nd][2][E][n] or None; diags[g][i] [E][n] or None -> the canonical residues of out, [2][L][n] (dtype object)"""
-    n, E = 1 << logn, L + k
-    D = model_digits(orc, logn, mext, L, k, alpha, np.ascontiguousarray(ct[1]))
-    baby = [model_switch_ext(orc, logn, mext, L, k, alpha, ct, key, s, c, D) for key, s, c in zip(bkeys, bsteps, bconj)]
-    acc = [[np.zeros(n, dtype=object) for _ in range(E)] for _ in range(2)]
-    for g, (key, s, c) in enumerate(zip(gkeys, gsteps, gconj)):
-        pre = [[np.zeros(n, dtype=object) for _ in range(E)] for _ in range(2)]
-        for i, dg in enumerate(diags[g]):
-            if dg is None:
-                continue
-            for h in range(2):
-                for m in range(E):
-                    pre[h][m] = (pre[h][m] + dg[m].astype(object) * baby[i][h][m]) % mext[m]
-        if key is not None:
-            u = mod_down(orc, logn, mext, L, k, pre).astype(U)
-            pre = model_switch_ext(orc, logn, mext, L, k, alpha, u, key, s, c)
-        for h in range(2):
-            for m in range(E):
-                acc[h][m] = (acc[h][m] + pre[h][m]) % mext[m]
-    return mod_down(orc, logn, mext, L, k, acc)
-
-
-def residues_match(got, exp, q):
-    """got [2][L][n] u64 against exp [2][L][n] Python integers: the same residues, every word below 2q"""
-    qa = np.array(q, dtype=U)[None, :, None]
-    assert (got < 2 * qa).all()
-    return np.array_equal((got % qa).astype(object), exp)
-
-
-def dev(eng, xs):
-    return [None if x is None else eng.to_device(x) for x in xs]
-
-
+# ---- running a case ------------------------------------------------------------------------------------------------------------
 def run(eng, mext, k, alpha, d_ct, bkeys, bsteps, bconj, gkeys, gsteps, gconj, diags):
     return eng.to_host(eng.ckks_lintrans_bsgs_hks(mext, k, alpha, d_ct, dev(eng, bkeys), bsteps, dev(eng, gkeys), gsteps,
                                                   [dev(eng, row) for row in diags], bconj, gconj))
@@ -188,21 +112,6 @@ def test_both_entries_the_identity_is_the_product_with_the_diagonal(eng, orc):
 
 
 # ---- (b) one identity giant: the flat call ----------------------------------------------------------------------------------------
-def flat_case(eng, logn, L, k, alpha, seed=7200, mext=None):
-    mext = mext or P.P40[:L] + P.P50[:k]
-    n = 1 << logn
-    rng = SplitMix(seed + logn)
-    steps, conj = [1, 0, 5], [False, True, False]
-    ct = rng.poly((2, 2, L, n), mext[:L])
-    dkeys = [eng.to_device(rng.poly(((L + alpha - 1) // alpha, 2, L + k, n), mext)) for _ in steps]
-    ddiags = [eng.to_device(random_diagonal(rng, mext, n)) for _ in steps]
-    d_ct = eng.to_device(ct)
-    flat = eng.to_host(eng.ckks_lintrans_hks(mext, k, alpha, d_ct, dkeys, steps, ddiags, conj))
-    bsgs = eng.to_host(eng.ckks_lintrans_bsgs_hks(mext, k, alpha, d_ct, dkeys, steps, [None], [0], [ddiags], conj))
-    qa = np.array(mext[:L], dtype=U)[None, None, :, None]
-    return flat % qa, bsgs % qa, bool((bsgs < 2 * qa).all())
-
-
 @pytest.mark.parametrize("logn,L,k,alpha", [(5, 4, 2, 2), (11, 3, 2, 2)])
 def test_one_identity_giant_is_the_flat_call(eng, logn, L, k, alpha):
     flat, bsgs, lazy = flat_case(eng, logn, L, k, alpha)

@@ -4,9 +4,9 @@ before ONE ModDown.
 The contract is on residues:
     acc[h][m] = sum_r diag_r[m] * ( sum_d move_r(D[d][m]) * key_r[d][h][m] )           for all L + k moduli m
     out[h]    = ModDown(acc[h]) + (h == 0) * sum_r diag_r[:L] * move_r(c0)              (mod each q_i), every word below 2 q_i
-with D the digit rows of the unrotated c1 (test_gpu_hks_hoisted.model_digits), the keys in Montgomery form as for every hybrid call
+with D the digit rows of the unrotated c1 (hks_model.model_digits), the keys in Montgomery form as for every hybrid call
 (the inner sum carries their 2^-64) and the diagonals plain words.  Pinned
-  (a) by that model written with Python integers, ModDown being test_gpu_hks_hoisted.model_rest's;
+  (a) by that model written with Python integers (hks_model.model_lintrans), ModDown being hks_model.model_rest's;
   (b) against hp_dev_ckks_rotate_hoisted_hks where the two must agree (one rotation, no diagonal);
   (c) against the weighted sum of the hoisted call's results: one rounding against R;
   (d) by decryption with keys generated here, for the device's words and for the model's;
@@ -17,9 +17,9 @@ import numpy as np
 import pytest
 
 import params as P
+from hks_model import (centred_error, chain, decryption_setup, model_lintrans, move, random_diagonal, residues_match, rotations_of,
+                       single_case)
 from oracle.pyoracle import SplitMix
-from test_gpu_hks_hoisted import chain, decryption_setup, model_digits, model_rest, move, rotations_of
-from test_hks import centred_error, crt, keygen  # noqa: F401  (crt, keygen: what decryption_setup and the model are made of)
 
 pytestmark = pytest.mark.gpu
 U = np.uint64
@@ -32,52 +32,6 @@ def eng():
     e = Engine(0)
     yield e
     e.close()
-
-
-# ---- the model -----------------------------------------------------------------------------------------------------------------
-def model_lintrans(orc, logn, mext, L, k, alpha, ct, keys, steps, conj, diags):
-    """ct [2][L][n], keys[r] [nd][2][E][n], diags[r] [E][n] or None -> the canonical residues of out, [2][L][n] (dtype object)"""
-    n, E = 1 << logn, L + k
-    D = model_digits(orc, logn, mext, L, k, alpha, ct[1])
-    acc = [[np.zeros(n, dtype=object) for _ in range(E)] for _ in range(2)]
-    c0sum = [np.zeros(n, dtype=object) for _ in range(L)]
-    for key, step, cj, dg in zip(keys, steps, conj, diags):
-        Dm = np.stack([move(orc, D[d], step, cj) for d in range(D.shape[0])]).astype(object)
-        c0m = move(orc, ct[0], step, cj).astype(object)
-        Ko = key.astype(object)
-        for m in range(E):
-            q, w = mext[m], (1 if dg is None else dg[m].astype(object))
-            unmont = pow(1 << 64, -1, q)                                  # the inner sum's one Montgomery reduction
-            for h in range(2):
-                inner = sum(Dm[d, m] * Ko[d, h, m] for d in range(D.shape[0])) * unmont % q
-                acc[h][m] = (acc[h][m] + w * inner) % q
-            if m < L:
-                c0sum[m] = (c0sum[m] + w * c0m[m]) % q
-    # ModDown of model_rest: its inner product with the "key" (2^64 mod q on the diagonal) hands the accumulator through unchanged
-    A = np.array(acc, dtype=object).astype(U)
-    unit = np.zeros((2, 2, E, n), dtype=U)
-    for m in range(E):
-        unit[0, 0, m, :] = unit[1, 1, m, :] = (1 << 64) % mext[m]
-    out = model_rest(orc, logn, mext, L, k, A, unit).astype(object)
-    for m in range(L):
-        out[0, m] = (out[0, m] + c0sum[m]) % mext[m]
-        out[1, m] = out[1, m] % mext[m]
-    return out
-
-
-def random_diagonal(rng, mext, n):
-    """[E][n] plain lazy words, half of them in [q, 2q)"""
-    E = len(mext)
-    d = rng.poly((E, n), mext)
-    upper = rng.words(E * n, 2).reshape(E, n).astype(U)
-    return d + upper * np.array(mext, dtype=U)[:, None]
-
-
-def residues_match(got, exp, q):
-    """got [2][L][n] u64 against exp [2][L][n] Python integers: the same residues, every word below 2q"""
-    qa = np.array(q, dtype=U)[None, :, None]
-    assert (got < 2 * qa).all()
-    return np.array_equal((got % qa).astype(object), exp)
 
 
 # ---- (a) the exact model --------------------------------------------------------------------------------------------------------
@@ -112,19 +66,6 @@ def test_lintrans_matches_the_exact_model(eng, orc, logn, L, k, alpha, B, R):
 
 
 # ---- (b) one rotation without a diagonal is the hoisted rotation ---------------------------------------------------------------------
-def single_case(eng, logn, L, k, alpha, seed=6200, mext=None):
-    mext = mext or P.P40[:L] + P.P50[:k]
-    n = 1 << logn
-    rng = SplitMix(seed + logn)
-    ct = rng.poly((2, 2, L, n), mext[:L])
-    key = rng.poly(((L + alpha - 1) // alpha, 2, L + k, n), mext)
-    d_ct, d_key = eng.to_device(ct), eng.to_device(key)
-    hoisted = eng.to_host(eng.ckks_rotate_hoisted_hks(mext, k, alpha, d_ct, [d_key], [3]))[:, 0]
-    lin = eng.to_host(eng.ckks_lintrans_hks(mext, k, alpha, d_ct, [d_key], [3], [None]))
-    qa = np.array(mext[:L], dtype=U)[None, None, :, None]
-    return hoisted % qa, lin % qa, bool((lin < 2 * qa).all())
-
-
 @pytest.mark.parametrize("logn,L,k,alpha", [(5, 4, 2, 2), (11, 3, 2, 2)])
 def test_one_rotation_without_a_diagonal_is_the_hoisted_rotation(eng, logn, L, k, alpha):
     hoisted, lin, lazy = single_case(eng, logn, L, k, alpha)
@@ -266,7 +207,7 @@ def test_lintrans_rejects_bad_arguments_before_enqueuing(eng):
 
     good = (1, 2, [1, 2], [kp, kp], [dp, None], ct.data_ptr(), out.data_ptr())
     assert call(*good) == capi.HP_OK
-    for bad in (dict(alpha_=0), dict(alpha_=9), dict(k_=0), dict(k_=17)):                                   # the limits of hks_args_ok
+    for bad in (dict(alpha_=0), dict(alpha_=9), dict(k_=0), dict(k_=17)):                                   # the limits every hybrid call checks
         assert call(*good, **bad) == capi.HP_EINVAL, bad
     assert call(0, 2, [1, 2], [kp, kp], [dp, None], ct.data_ptr(), out.data_ptr()) == capi.HP_EINVAL          # empty batch
     assert call(1, 0, [], [], [], ct.data_ptr(), out.data_ptr()) == capi.HP_EINVAL                            # no rotations

@@ -4,11 +4,11 @@ tests/moduli.py cut to (L, k) and WIDE58 (tests/hks_edges.py: every modulus 58 o
   * the 128-bit sums of k_hks_inner_lintrans and k_hks_bsgs_presum come within 2.5 bits of wrapping (tests/test_hks_edges.py has the
     figures, computed with Python integers, and asserts the registers' conditions without a GPU);
   * the fix = 1 fold, the per-limb pack-48 decision and the level-A eligibility decision switch.
-The models are those of the three calls' own test files: Python integers around the oracle's primitives.
+The models are those of the three calls' own tests (tests/hks_model.py): Python integers around the oracle's primitives.
 What these cases found: at a high_mid ciphertext modulus the lazy transform of ModDown's remainder has words of 2q and more, on which
 hehub's lazy subtraction wraps -- the residues then depended on which representative the accumulator word happened to be, and the
 three calls disagreed with each other on those limbs (case 6, which needs no model) and with plain integer arithmetic.  The ModDown kernels and
-the model now bring the remainder's words below 2q first (hp_lazy_below_2q, hp_device.h; test_hks.below_2q), which changes no word
+the model now bring the remainder's words below 2q first (hp_lazy_below_2q, hp_device.h; hks_model.below_2q), which changes no word
 where they already were; tests/test_hks_edges.py holds the model's ModDown to plain integer arithmetic at such moduli.
   (1) the exact model on every chain: hoisted word for word at level B, the two transforms on residues with every word below 2q;
   (2) extremal rows: every (polynomial, limb) row of ciphertext, keys and diagonals one of moduli.INPUT_KINDS, and everything 2q - 1;
@@ -20,9 +20,7 @@ import pytest
 
 import hks_edges as H
 import moduli as M
-from test_gpu_hks_bsgs import flat_case, model_bsgs
-from test_gpu_hks_hoisted import model_hoisted, step0_case
-from test_gpu_hks_lintrans import model_lintrans, residues_match, single_case
+from hks_model import dev, flat_case, model_bsgs, model_hoisted, model_lintrans, residues_match, single_case, step0_case
 from test_gpu_moduli import LEVEL_A_CHAINS
 
 pytestmark = pytest.mark.gpu
@@ -44,10 +42,6 @@ def seed_of(name, logn, L):
 
 
 # ---- running a case of hks_edges on the device, and its model ----------------------------------------------------------------------
-def dev(eng, xs):
-    return [None if x is None else eng.to_device(x) for x in xs]
-
-
 def run_hoisted(eng, c):
     dk = dev(eng, c["kpool"])
     return eng.to_host(eng.ckks_rotate_hoisted_hks(c["mext"], c["k"], c["alpha"], eng.to_device(c["ct"]), H.pick(dk, c["which"]), c["steps"],
@@ -272,4 +266,4 @@ def test_the_three_calls_agree_where_they_must(eng, name):
     flat, bsgs, lazy = flat_case(eng, logn, L, k, alpha, mext=mext)
     assert lazy and np.array_equal(flat, bsgs)                         # one identity giant is the flat call
     plain, hoisted = step0_case(eng, logn, L, k, alpha, mext=mext)
-    assert np.array_equal(plain, hoisted)                              # hoisted step 0 is the unhoisted rotation (hks_switch plus c0)
+    assert np.array_equal(plain, hoisted)                              # hoisted step 0 is the unhoisted rotation (one switch plus c0)

@@ -196,7 +196,7 @@ def test_knobs_leave_the_words_alone(monkeypatch, orc, name, env):
 
 @pytest.mark.parametrize("name", ["W59", "ABOVE"])
 def test_hybrid_key_switch(eng, orc, name):
-    from test_hks import model_switch
+    from hks_model import model_switch
 
     logn, L, k, alpha = 11, 3, 2, 2
     mext = M.CHAINS[name][:L] + M.CHAINS[name][-k:]

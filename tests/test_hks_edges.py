@@ -19,12 +19,12 @@ import pytest
 import hks_edges as H
 import moduli as M
 import params as P
+from hks_model import chain, crt, model_lintrans, model_rest, rotations_of
 from oracle.pyoracle import SplitMix
-from test_gpu_hks_hoisted import chain, rotations_of
 from test_gpu_moduli import LEVEL_A_CHAINS
 
 U = np.uint64
-pytestmark = []          # (the modules this one borrows models from are GPU modules; this one is not)
+pytestmark = []          # (the module this one borrows LEVEL_A_CHAINS from is a GPU module; this one is not)
 
 
 def shapes_in_use():
@@ -140,8 +140,6 @@ def test_the_table_chains_never_carry(orc):
 
 # ---- the sampled model is the model -------------------------------------------------------------------------------------------------
 def test_sampled_model_is_the_model(orc):
-    from test_gpu_hks_lintrans import model_lintrans
-
     logn, L, k, alpha, R = 5, 5, 2, 2, 5
     c = H.flat_inputs("WIDE58", logn, L, k, alpha, 1, R, "kinds", 8500)
     keys, diags = H.pick(c["kpool"], c["which"]), H.pick(c["dpool"], c["wd"])
@@ -165,10 +163,7 @@ def test_model_moddown_is_exact_at_high_mid_moduli(orc, name):
         out_i = (x_i - [x]_P) * P^-1 mod q_i,   [x]_P the centred value of the special-prime part, coefficient by coefficient.
     At a high_mid modulus the lazy transform of the remainder has words of 2q and more; hehub's lazy subtraction takes its operand below
     2q and wraps on them (70 % of the words of such a limb at N = 2048), so the remainder's words are brought below 2q first
-    (test_hks.below_2q; hp_lazy_below_2q on the device).  Without that this test fails on the high_mid limbs only."""
-    from test_gpu_hks_hoisted import model_rest
-    from test_hks import crt
-
+    (hks_model.below_2q; hp_lazy_below_2q on the device).  Without that this test fails on the high_mid limbs only."""
     logn, L, k = 11, 3, 2
     mext, n, E = H.chain_of(name, L, k), 1 << logn, L + k
     q, pm = mext[:L], mext[L:]

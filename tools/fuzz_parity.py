@@ -97,7 +97,7 @@ while time.time() - t0 < budget:
             check("to_single", eng.to_host(eng.rns_base_to_single(q, t, eng.to_device(xs))),
                   np.stack([orc.rns_base_to_single(q, t, xs[i]) for i in range(B)]), t=t, **kw)
     elif op == "hks":
-        from test_hks import model_switch
+        from hks_model import model_switch
         logn = int(rs.choice([1, 2, 3, 4, 5, 11], p=[.1, .15, .2, .25, .25, .05])); n = 1 << logn
         L = int(rs.randint(1, 7)); alpha = int(rs.randint(1, min(L, 8) + 1)); k = int(rs.randint(1, 5))
         idx = rs.choice(len(pool), L + k, replace=False)
