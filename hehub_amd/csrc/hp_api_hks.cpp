@@ -2,6 +2,7 @@
 // kernels in hp_hks.hip.  Exact integer arithmetic throughout (ModUp / ModDown by mixed-radix composition); keys have
 // their own format, so results are pinned by an exact integer model and by decryption, not by hehub's words.
 #include "hp_ctx.h"
+#include "hp_ntt_job.h"   // item counts
 
 #include <algorithm>
 #include <cstring>
@@ -152,7 +153,7 @@ struct HksCall {
         memset(&j, 0, sizeof(j));
         j.limbs = plan->d_limbs; j.src = lifted; j.dst = lifted; j.logn = (u32)logn; j.L = (u32)L; j.P = (u32)P;
         j.hks_nd = (u32)nd; j.hks_E = (u32)E; j.hks_alpha = (u32)alpha; j.mode = HP_NTT_HKS;
-        j.W = (u32)(L * (nd - 1) * P + k * nd * P);
+        j.W = hp_hks_items((u32)L, (u32)nd, (u32)k, (u32)P);
         // parity level A: the lifted rows are canonical residues (ModUp's exact conversion), the inner product takes any
         // representative, and hybrid results have no word-level contract with hehub (other keys): the FP64 transform where allowed
         if (ctx->cur_a) j.limbs_a = plan->d_limbs_a;

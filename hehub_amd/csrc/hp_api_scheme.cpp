@@ -3,6 +3,7 @@
 // rotations (ckks/arith.cpp:64-93, bgv/arith.cpp:71-79), the fused mult pipelines, and the limb-range stages of the
 // limb-sharded multi-GPU mode.
 #include "hp_ctx.h"
+#include "hp_ntt_job.h"   // item counts
 
 #include <algorithm>
 #include <cstring>
@@ -67,9 +68,7 @@ int ks_digits_inner(hp_ctx *ctx, const Plan *plan, size_t logn, size_t L, size_t
     HpNttJob sj;
     memset(&sj, 0, sizeof(sj));
     sj.limbs = plan->d_limbs; sj.src = coef; sj.dst = digits; sj.logn = (u32)logn; sj.L = (u32)L; sj.P = (u32)P;
-    // items: (L-1)*P per modulus k < L (the diagonal digit is not transformed), L*P for the special prime k = L
-    const size_t n_lo = (k1 < L ? k1 : L) - (k0 < L ? k0 : L);
-    sj.k_first = (u32)k0; sj.W = (u32)(n_lo * (L - 1) * P + (k1 > L ? L * P : 0)); sj.mode = HP_NTT_SPREAD;
+    sj.k_first = (u32)k0; sj.W = hp_spread_items((u32)L, (u32)P, (u32)k0, (u32)k1); sj.mode = HP_NTT_SPREAD;
     sj.pair_moduli = (k0 == 0 && k1 == L + 1 && L >= 2) ? (u32)ctx->spread_group : 0u;
     if (sj.pair_moduli > L) sj.pair_moduli = (u32)L;
     // digit rows of the output moduli whose words are provably below 2^48 cross HBM as 6 bytes per word (HP_PACK48)

@@ -48,6 +48,9 @@ struct HpLimbA {
 };
 
 #define HP_DEV __device__ __forceinline__
+// pure integer numbering (which rows a workgroup works on) that host code may call too: tests/test_host_ntt_items.py
+// enumerates it on the CPU
+#define HP_HD __host__ __device__ __forceinline__
 
 HP_DEV u64 hp_mulhi(u64 a, u64 b) { return __umul64hi(a, b); }
 
@@ -340,8 +343,26 @@ HP_DEV u64 hp_lazy_below_2q(u64 x, u64 two_q) {
 // (block b -> XCD b % 8, observed placement; used for L2 locality only).  Work
 // items are numbered so that neighbours share a modulus (twiddle table); this
 // map hands XCD x the contiguous slice [x*W/8, (x+1)*W/8).
-HP_DEV u32 hp_xcd_remap(u32 b, u32 W) {
+HP_HD u32 hp_xcd_remap(u32 b, u32 W) {
     const u32 per = W >> 3;
     if (b >= (per << 3)) return b; // tail that does not divide evenly
     return (b & 7u) * per + (b >> 3);
 }
+
+// By-XCD numbering of `units` x W workgroups (hp_hks.hip: the hoisted and the diagonal inner products): of eight consecutive
+// block ids each goes to its own unit, so an XCD works through all W workgroups of one unit before it takes the next.  The
+// units that do not fill a group of eight are numbered plainly.  Every (unit, w) with unit < units, w < W is one block < units * W.
+// The arithmetic as statements, for k_hks_inner_lintrans: through the function the schedule of its baby flavour moves (two
+// independent instructions trade places), expanded in place it compiles to what it was.  Everything else calls hp_xcd_unit.
+#define HP_XCD_UNIT(block, units, W, unit, w) \
+    { \
+        const u32 grouped = ((units) & ~7u) * (W); \
+        if ((block) < grouped) { \
+            unit = ((block) / (8 * (W))) * 8 + ((block) & 7u); \
+            w = ((block) >> 3) % (W); \
+        } else { \
+            unit = ((units) & ~7u) + ((block) - grouped) / (W); \
+            w = ((block) - grouped) % (W); \
+        } \
+    }
+HP_HD void hp_xcd_unit(u32 block, u32 units, u32 W, u32 &unit, u32 &w) { HP_XCD_UNIT(block, units, W, unit, w) }

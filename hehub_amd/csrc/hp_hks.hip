@@ -136,15 +136,9 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner_hoisted(const HpLimb
                                                                   u32 P, u32 R, u32 n, u32 chunks, const u64 *__restrict__ lifted,
                                                                   const u64 *__restrict__ pt, u32 pt_pstride, HpHoistTable tab,
                                                                   u64 *__restrict__ out) {
-    const u32 PG = (P + PT - 1) / PT, units = E * PG, W = R * chunks, grouped = (units & ~7u) * W;
+    const u32 PG = (P + PT - 1) / PT, units = E * PG, W = R * chunks;
     u32 unit, w;
-    if (blockIdx.x < grouped) {
-        unit = (blockIdx.x / (8 * W)) * 8 + (blockIdx.x & 7u);
-        w = (blockIdx.x >> 3) % W;
-    } else {
-        unit = (units & ~7u) + (blockIdx.x - grouped) / W;
-        w = (blockIdx.x - grouped) % W;
-    }
+    hp_xcd_unit(blockIdx.x, units, W, unit, w);
     const u32 m = unit / PG, p0 = (unit % PG) * PT, r = w / chunks;
     const ElemTile tile(ElemTile::At{unit, w % chunks}, n);
     const u64 q = limbs[m].q, mqinv = limbs[m].mqinv;
@@ -250,15 +244,9 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner_lintrans(const HpLim
                                                                    const u64 *__restrict__ lifted, const u64 *__restrict__ ct,
                                                                    HpLinTable tab, u32 add_prev, u64 *__restrict__ out) {
     const u32 L = hc->L, E = hc->E, nd = hc->nd, alpha = hc->alpha;
-    const u32 units = E * P, W = FLAV == HKS_LT_BABY ? R * chunks : chunks, grouped = (units & ~7u) * W;
+    const u32 units = E * P, W = FLAV == HKS_LT_BABY ? R * chunks : chunks;
     u32 unit, w;
-    if (blockIdx.x < grouped) {
-        unit = (blockIdx.x / (8 * W)) * 8 + (blockIdx.x & 7u);
-        w = (blockIdx.x >> 3) % W;
-    } else {
-        unit = (units & ~7u) + (blockIdx.x - grouped) / W;
-        w = (blockIdx.x - grouped) % W;
-    }
+    HP_XCD_UNIT(blockIdx.x, units, W, unit, w)   // (hp_device.h: why not the function here)
     const u32 m = unit / P, p = unit % P;
     const ElemTile tile(ElemTile::At{unit, w % chunks}, n, HKS_LT_CHUNK);
     const u32 r_first = FLAV == HKS_LT_BABY ? w / chunks : 0, r_end = FLAV == HKS_LT_BABY ? r_first + 1 : R;

@@ -1,4 +1,6 @@
-// hp_ntt_job.h -- decoding of a transform work item (shared by the generic and tiled kernels).
+// hp_ntt_job.h -- decoding of a transform work item (shared by the generic and tiled kernels), and the item counts the
+// launches are sized with.  Integer arithmetic only, callable from host code: tests/test_host_ntt_items.py enumerates every
+// item of every shape family on the CPU (through tests/cpp/ntt_items_shim.cpp) and compares with the sets written out there.
 #pragma once
 #include "hp_kernels.h"
 
@@ -9,9 +11,21 @@ struct HpItem {
     u32 poly;   // HP_NTT_BATCH: the polynomial of the item
 };
 
+// ---- item counts (HpNttJob::W) ------------------------------------------------------------------
+// HP_NTT_SPREAD over the output moduli [k0, k1) of 0..L: (L-1)*P items per modulus k < L (the diagonal digit is not
+// transformed), L*P for the special prime k = L
+HP_HD u32 hp_spread_items(u32 L, u32 P, u32 k0, u32 k1) {
+    const u32 n_lo = (k1 < L ? k1 : L) - (k0 < L ? k0 : L);
+    return n_lo * (L - 1) * P + (k1 > L ? L * P : 0);
+}
+// HP_NTT_HKS: a ciphertext modulus is outside nd-1 digits, each of the k special primes outside all nd
+HP_HD u32 hp_hks_items(u32 L, u32 nd, u32 k, u32 P) { return L * (nd - 1) * P + k * nd * P; }
+// workgroups of a tiled inverse launch with LPW polynomials of one modulus per workgroup (hp_ntt_tile.h: InvGeo)
+HP_HD u32 hp_inv_grid(const HpNttJob &job, u32 LPW) { return LPW == 1 ? job.W : job.L * ((job.P + LPW - 1) / LPW); }
+
 // (digit spread: the diagonal digit k == j is never an item -- it is the untouched NTT-form input limb,
 // rgsw.cpp:99-101, read directly by the inner-product kernel)
-HP_DEV bool hp_decode_item(const HpNttJob &job, u32 w, HpItem &it) {
+HP_HD bool hp_decode_item(const HpNttJob &job, u32 w, HpItem &it) {
     const size_t n = (size_t)1 << job.logn;
     if (job.mode == HP_NTT_BATCH) {
         u32 k = w / job.P, p = w % job.P;
@@ -93,4 +107,32 @@ HP_DEV bool hp_decode_item(const HpNttJob &job, u32 w, HpItem &it) {
         return true;
     }
     return false;
+}
+
+// Tiled inverse launches (hp_ntt_tile.h: inv_item): the item of sub-limb `sub` of workgroup `block` when a workgroup transforms
+// LPW polynomials of ONE modulus side by side; n = words per row (a compile-time constant in the kernels).  false: a group past
+// the last polynomial, which re-reads the last one and stores nothing.
+// (every inverse launch is HP_NTT_BATCH without groups: the launchers reject anything else)
+HP_HD bool hp_inv_item(const HpNttJob &job, u32 block, u32 sub, u32 LPW, size_t n, HpItem &it) {
+    bool active = true;
+    if (LPW == 1) {
+        const u32 w = hp_xcd_remap(block, job.W);
+        const u32 k = w / job.P, p = w % job.P;
+        it.src = job.src + ((size_t)p * job.src_pstride + (size_t)k * job.src_kstride) * n;
+        it.dst = job.dst + ((size_t)p * job.dst_pstride + k) * n;
+        it.limb = k;
+        it.poly = p;
+    } else {
+        // ceil(P / LPW) workgroups per modulus, modulus-major like the item numbering
+        const u32 bpm = (job.P + LPW - 1) / LPW;
+        const u32 wb = hp_xcd_remap(block, job.L * bpm);
+        const u32 k = wb / bpm, p0 = (wb % bpm) * LPW + sub;
+        active = p0 < job.P;
+        const u32 p = active ? p0 : job.P - 1;
+        it.src = job.src + ((size_t)p * job.src_pstride + (size_t)k * job.src_kstride) * n;
+        it.dst = job.dst + ((size_t)p * job.dst_pstride + k) * n;
+        it.limb = k;
+        it.poly = p;
+    }
+    return active;
 }

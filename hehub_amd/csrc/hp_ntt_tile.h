@@ -525,35 +525,13 @@ template <int LOGN> struct InvGeo {
     static constexpr int TT = Geo<LOGN>::T * LPW;                      // threads per workgroup
     static constexpr bool STREAM_EPILOGUE = LOGN <= 13;                // see the end of k_ntt_inv
     static constexpr int NSTG = (31 * 32 + TT - 1) / TT;               // staged twiddle pairs per thread
-    static u32 grid(const HpNttJob &job) { return LPW == 1 ? job.W : job.L * ((job.P + LPW - 1) / LPW); }
+    static u32 grid(const HpNttJob &job) { return hp_inv_grid(job, LPW); }
 };
 
 // the item of sub-limb `sub` of a workgroup; false: a group past the last polynomial, which re-reads the last one and stores nothing
-// (every inverse launch is HP_NTT_BATCH without groups: the launchers reject anything else)
+// (the numbering itself: hp_inv_item, hp_ntt_job.h)
 template <int LOGN> HP_DEV bool inv_item(const HpNttJob &job, u32 sub, HpItem &it) {
-    using G = Geo<LOGN>;
-    constexpr int LPW = InvGeo<LOGN>::LPW;
-    bool active = true;
-    if (LPW == 1) {
-        const u32 w = hp_xcd_remap(blockIdx.x, job.W);
-        const u32 k = w / job.P, p = w % job.P;
-        it.src = job.src + ((size_t)p * job.src_pstride + (size_t)k * job.src_kstride) * G::N;
-        it.dst = job.dst + ((size_t)p * job.dst_pstride + k) * G::N;
-        it.limb = k;
-        it.poly = p;
-    } else {
-        // ceil(P / LPW) workgroups per modulus, modulus-major like the item numbering
-        const u32 bpm = (job.P + LPW - 1) / LPW;
-        const u32 wb = hp_xcd_remap(blockIdx.x, job.L * bpm);
-        const u32 k = wb / bpm, p0 = (wb % bpm) * LPW + sub;
-        active = p0 < job.P;
-        const u32 p = active ? p0 : job.P - 1;
-        it.src = job.src + ((size_t)p * job.src_pstride + (size_t)k * job.src_kstride) * G::N;
-        it.dst = job.dst + ((size_t)p * job.dst_pstride + k) * G::N;
-        it.limb = k;
-        it.poly = p;
-    }
-    return active;
+    return hp_inv_item(job, blockIdx.x, sub, InvGeo<LOGN>::LPW, Geo<LOGN>::N, it);
 }
 
 // ---- launch dispatch -------------------------------------------------------------------------------

@@ -1,7 +1,7 @@
 """The tiled transforms (hp_ntt_fast.hip, hp_ntt_a.hip over hp_ntt_tile.h) reached on purpose: small batches go through
 hp_ntt_split.hip, so every case here opens its own engine with HP_SPLIT_MAX_ITEMS=0 and runs each compiled flavour of the fused drop
 and both parity levels at the ring degrees whose code paths differ:
-    N = 2048, 8192   several limbs per workgroup in the inverse kernels, stream epilogue
+    N = 2048, 4096, 8192   eight / four / two limbs per workgroup in the inverse kernels, stream epilogue
     N = 16384        one limb per workgroup, layout-A store with passenger bits
     N = 32768        lane-pair loads / stores, padded exchange buffer
 One wide (50-bit) and two narrow (40-bit) limbs under a 50-bit special prime; the largest canonical and the largest lazy word planted
@@ -19,7 +19,7 @@ U = np.uint64
 MEXT = [P.P50[1], P.P40[0], P.P40[1], P.P50[0]]
 L, B, T = 3, 2, 65537
 Q = MEXT[:L]
-LOGNS = [11, 13, 14, 15]
+LOGNS = [11, 12, 13, 14, 15]
 _expected = {}
 
 
