@@ -516,6 +516,28 @@ class Engine:
                                                  self._ptr(tmp) if tmp is not None else None, self._ptr(out)))
         return out
 
+    # -- limb-range stages of the drop (the calls hehub_amd/sharded.py makes) ----
+    def drop_coeffs(self, moduli, t: int, x):
+        """x [..][L][n] -> the strict coefficients [P2][n] of every polynomial's last limb (t != 0: BGV, times t^-1)"""
+        L, n = x.shape[-2:]
+        P2 = x.numel() // (L * n)
+        clast = self.empty((P2, n))
+        self._chk(self.lib.hp_dev_drop_coeffs(self.h, n.bit_length() - 1, L, _u64arr(moduli), t, P2, self._ptr(x), self._ptr(clast)))
+        return clast
+
+    def drop_apply_range(self, moduli, t: int, x, clast, k0: int, k1: int, addend=None, add_mask: int = 0, strict: bool = False, out=None):
+        """the drop of the last modulus on the limbs [k0, k1) of x [..][L][n] given the coefficient rows clast [P2][n] -> [P2][L-1][n]
+        (only those limbs are written).  addend: [B][2][La][n], polynomial h of each ciphertext gets its rows where bit h of add_mask is
+        set.  strict: the caller vouches that every word of clast is below the last modulus (hp_dev_drop_apply_range_strict)."""
+        L, n = x.shape[-2:]
+        P2 = x.numel() // (L * n)
+        out = self.empty((P2, L - 1, n)) if out is None else out
+        fn = self.lib.hp_dev_drop_apply_range_strict if strict else self.lib.hp_dev_drop_apply_range
+        La = addend.shape[-2] if addend is not None else 0
+        self._chk(fn(self.h, n.bit_length() - 1, L, _u64arr(moduli), t, P2, k0, k1, self._ptr(x), self._ptr(clast),
+                     self._ptr(addend) if addend is not None else None, La, 2 * La, add_mask if addend is not None else 0, self._ptr(out)))
+        return out
+
     # -- either side of the path -------------------------------------------
     def rlwe_encrypt_core(self, moduli, noise, c1, pt, sk):
         B, L, n = c1.shape
