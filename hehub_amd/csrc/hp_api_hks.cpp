@@ -609,3 +609,103 @@ extern "C" int hp_dev_ckks_mult_relin_rescale_hks(hp_ctx *ctx, size_t logn, size
     if ((rc = c.key_switch(batch, quad + 2 * L * n, 3 * L, key, Addend(quad, L, 3 * L, 3), lin, cv))) return rc;
     return drop_last(ctx, plan, logn, L, 2 * batch, false, 0, lin, Addend(), out, cv);
 }
+
+// ---- key generation ----------------------------------------------------------------------------------------------------------------
+// Sampling stays with the caller (the uniform rows a and the error polynomials e are inputs); what runs here is the arithmetic:
+// spread (k_spread_signed) -> one batched forward transform -> one fused multiply-add (k_hks_keygen).  The error rows are spread
+// into d_keys[r][d][0] and transformed there in place (a batch job with a polynomial stride of 2E rows); the fused kernel reads each
+// word before it overwrites it.  No workspace.
+constexpr size_t KEYGEN_MAX_BLOCKS = (size_t)1 << 30;   // workgroups per launch (and, with it, every u32 row count below)
+static size_t keygen_chunks(size_t n) { return (n + 2047) / 2048; }   // (ELEM_CHUNK words per workgroup, hp_elem.h)
+
+// small signed polynomials -> NTT form
+extern "C" int hp_dev_poly_from_signed(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, size_t batch, const int64_t *d_coeffs,
+                                       uint64_t *d_out) {
+    HP_ENTER(ctx);
+    HP_REQUIRE(ctx, moduli, d_coeffs, d_out);
+    HP_ALIGNED(ctx, d_coeffs, d_out);
+    if (!logn_ok(logn)) return fail(ctx, HP_EUNSUPPORTED, HP_LOGN_MSG);
+    if (L < 1 || L > HP_MAX_LIMBS) return fail(ctx, HP_EINVAL, "unsupported number of moduli");
+    if (batch == 0) return fail(ctx, HP_EINVAL, "empty batch");
+    const size_t n = (size_t)1 << logn, chunks = keygen_chunks(n);
+    if (batch > KEYGEN_MAX_BLOCKS / (L * chunks)) return fail(ctx, HP_EUNSUPPORTED, "poly_from_signed: too many polynomials for one call");
+    int rc = no_overlap(ctx, "poly_from_signed", d_coeffs, batch * n * 8, d_out, batch * L * n * 8);
+    if (rc) return rc;
+    const Plan *plan;
+    if ((rc = get_plan(ctx, logn, moduli, L, true, &plan))) return rc;
+    {
+        ProfScope ps(ctx, "spread_signed");
+        if ((rc = chk(ctx, hp_launch_spread_signed(plan->d_limbs, (u32)L, (u32)n, (u32)batch, (const long long *)d_coeffs, d_out, (u32)L,
+                                                   ctx->stream), "spread_signed")))
+            return rc;
+    }
+    return run_ntt(ctx, batch_job(plan, logn, L, batch, d_out, d_out, L, L, 0, 0));   // hp_dev_ntt's launch: its words
+}
+
+// rot == NULL: d_from = s_from [keys][E][N]; else the source secret of key r is move_r(d_s_to), read through the rotation's map
+static int dev_hks_keygen(hp_ctx *ctx, const char *call, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *mext, size_t keys,
+                          const HksRotations *rot, const uint64_t *d_s_to, const uint64_t *d_from, const uint64_t *d_a, const int64_t *d_e,
+                          uint64_t *d_keys) {
+    HksCall c(ctx, logn, L, k, alpha, mext, keys);
+    if (c.rc) return c.rc;
+    const size_t n = c.n, E = c.E, nd = c.nd, chunks = keygen_chunks(n);
+    int rc;
+    for (size_t r = 0; rot && r < keys; r++)
+        if (!(rot->conj && rot->conj[r]) && rot->steps[r] >= ((size_t)1 << 17)) return fail(ctx, HP_EINVAL, "rotation step out of range");
+    if (keys > KEYGEN_MAX_BLOCKS / (nd * 2 * E * chunks)) return fail(ctx, HP_EUNSUPPORTED, std::string(call) + ": too many keys for one call");
+    const size_t out_bytes = keys * nd * 2 * E * n * 8;
+    if ((rc = no_overlap(ctx, call, d_s_to, E * n * 8, d_keys, out_bytes)) || (rc = no_overlap(ctx, call, d_e, keys * nd * n * 8, d_keys, out_bytes)) ||
+        (d_from && (rc = no_overlap(ctx, call, d_from, keys * E * n * 8, d_keys, out_bytes))) ||
+        (d_a && (rc = no_overlap(ctx, call, d_a, keys * nd * E * n * 8, d_keys, out_bytes))))
+        return rc;
+    if (c.open()) return c.rc;
+    const Plan *plan = c.plan;
+    {
+        ProfScope ps(ctx, "spread_signed");
+        if ((rc = chk(ctx, hp_launch_spread_signed(plan->d_limbs, (u32)E, (u32)n, (u32)(keys * nd), (const long long *)d_e, d_keys, (u32)(2 * E),
+                                                   ctx->stream), "spread_signed")))
+            return rc;
+    }
+    {
+        HpNttJob j = batch_job(plan, logn, E, keys * nd, d_keys, d_keys, 2 * E, 2 * E, 0, 0);
+        if (ctx->cur_a) j.limbs_a = plan->d_limbs_a;   // strict rows in, any representative out: the FP64 transform where allowed
+        if ((rc = run_ntt(ctx, j))) return rc;
+    }
+    // one launch; a rotation list longer than one argument table: one launch per table
+    const size_t pass = rot ? std::min<size_t>(keys, HP_HOIST_TABLE_MAX) : keys;
+    for (size_t r0 = 0; r0 < keys; r0 += pass) {
+        const size_t cnt = std::min(pass, keys - r0);
+        HpKeygenMaps maps;
+        memset(&maps, 0, sizeof(maps));
+        if (rot) {
+            if ((rc = reserve_cycle_perms(ctx, cnt))) return rc;   // (a miss in a full map cache empties it: not between these)
+            for (size_t r = 0; r < cnt; r++)
+                if (!(rot->conj && rot->conj[r0 + r]) && (rc = get_cycle_perm(ctx, logn, rot->steps[r0 + r], &maps.map[r]))) return rc;
+        }
+        ProfScope ps(ctx, "hks_keygen");
+        if ((rc = chk(ctx, hp_launch_hks_keygen(plan->d_limbs, c.he->dev, (u32)E, (u32)nd, (u32)n, (u32)cnt, d_s_to,
+                                                d_from ? d_from + r0 * E * n : nullptr, rot ? &maps : nullptr,
+                                                d_a ? d_a + r0 * nd * E * n : nullptr, d_keys + r0 * nd * 2 * E * n, ctx->stream), call)))
+            return rc;
+    }
+    return HP_OK;
+}
+
+extern "C" int hp_dev_hks_keygen(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t keys,
+                                 const uint64_t *d_s_to, const uint64_t *d_s_from, const uint64_t *d_a, const int64_t *d_e, uint64_t *d_keys) {
+    HP_ENTER(ctx);
+    HP_REQUIRE(ctx, moduli_ext, d_s_to, d_s_from, d_e, d_keys);
+    HP_ALIGNED(ctx, d_s_to, d_s_from, d_a, d_e, d_keys);
+    return dev_hks_keygen(ctx, "hks_keygen", logn, L, k, alpha, moduli_ext, keys, nullptr, d_s_to, d_s_from, d_a, d_e, d_keys);
+}
+
+// the key that switches move_r(s) back to s: what hp_dev_ckks_rotate_hks and its kin apply to a ciphertext rotated by the same entry
+extern "C" int hp_dev_hks_keygen_rot(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t keys,
+                                     const size_t *steps, const unsigned char *conj, const uint64_t *d_s, const uint64_t *d_a,
+                                     const int64_t *d_e, uint64_t *d_keys) {
+    HP_ENTER(ctx);
+    HP_REQUIRE(ctx, moduli_ext, steps, d_s, d_e, d_keys);
+    HP_ALIGNED(ctx, d_s, d_a, d_e, d_keys);
+    const HksRotations rot = {keys, steps, conj, nullptr};
+    return dev_hks_keygen(ctx, "hks_keygen_rot", logn, L, k, alpha, moduli_ext, keys, &rot, d_s, nullptr, d_a, d_e, d_keys);
+}

@@ -71,6 +71,30 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_lift_noise(const HpLimb *__res
     }
 }
 
+// Small signed polynomials as residues (hp_dev_poly_from_signed, the error rows of hp_dev_hks_keygen): out row p*out_pstride + k =
+// coeffs[p] mod q_k, strict.  Unlike k_lift_noise this takes ANY int64_t: plain integer arithmetic -- Barrett on the magnitude
+// (|INT64_MIN| = 2^63 is a u64 like any other; hp_barrett_lazy is below 2q for every 64-bit word), then the conditional negation
+// q - r, where r = 0 stays 0.  Two coefficients per lane and round (n is even for every supported ring).  The coefficient row is
+// read by the L workgroups of its moduli and the residues by the transform that follows: ordinary loads and stores.
+__global__ void __launch_bounds__(ELEM_THREADS) k_spread_signed(const HpLimb *__restrict__ limbs, u32 L, u32 n, u32 chunks,
+                                                               const long long *__restrict__ coeffs, u64 *__restrict__ out,
+                                                               u32 out_pstride) {
+    const ElemTile tile(n, chunks);   // row = p*L + k
+    const u32 p = tile.row / L, k = tile.row % L;
+    const u64 q = limbs[k].q, bc = limbs[k].barrett_c;
+    const u64 *src = reinterpret_cast<const u64 *>(coeffs) + (size_t)p * n;
+    u64 *dst = out + ((size_t)p * out_pstride + k) * n;
+    const auto residue = [&](u64 c) {
+        const bool neg = (long long)c < 0;
+        const u64 r = hp_strict(hp_barrett_lazy(neg ? 0 - c : c, q, bc), q);
+        return (neg && r) ? q - r : r;
+    };
+    for (const u32 i : tile.pairs()) {
+        const U2 c = *reinterpret_cast<const U2 *>(src + i);
+        *reinterpret_cast<U2 *>(dst + i) = U2{residue(c.x), residue(c.y)};
+    }
+}
+
 // rlwe.cpp:52 and :70: c0 = (ex - c1*sk) + NTT(pt); ct[p] = (c0, c1).  ex is read from ct[p][0] (in place).
 __global__ void __launch_bounds__(ELEM_THREADS) k_enc_fin(const HpLimb *__restrict__ limbs, u32 L, u32 n, u32 chunks,
                                                          const u64 *__restrict__ c1, const u64 *__restrict__ sk,
@@ -141,6 +165,10 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_base_to_single(const HpLimb *_
 hipError_t hp_launch_lift_noise(const HpLimb *limbs, u32 L, u32 n, u32 P, const long long *noise, u64 *out, u32 out_pstride,
                                 hipStream_t stream) {
     return elem_launch(k_lift_noise, P * L, n, stream, limbs, L, n, ElemChunks{}, noise, out, out_pstride);
+}
+hipError_t hp_launch_spread_signed(const HpLimb *limbs, u32 L, u32 n, u32 P, const long long *coeffs, u64 *out, u32 out_pstride,
+                                   hipStream_t stream) {
+    return elem_launch(k_spread_signed, P * L, n, stream, limbs, L, n, ElemChunks{}, coeffs, out, out_pstride);
 }
 hipError_t hp_launch_enc_fin(const HpLimb *limbs, u32 L, u32 n, u32 P, const u64 *c1, const u64 *sk, const u64 *ptn, u64 *ct,
                              hipStream_t stream) {

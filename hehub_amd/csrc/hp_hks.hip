@@ -12,6 +12,7 @@
 //            when m belongs to digit d -- the same 128-bit accumulation as hehub's inner product
 //   ModDown  the P-part of the result, centred exactly (hp_edge.hip: k_base_to_single_crt), is subtracted and the rest
 //            multiplied by P^-1:  out = (x - NTT(rem)) * P^-1 [+ addend]
+//   keygen   the keys themselves from the caller's samples: key_d = ((NTT(e) - a s_to + [digit d] (P mod q) s_from) 2^64, a 2^64)
 // Tile skeleton, launch helpers and the Garner digits shared with hp_edge.hip: hp_elem.h.
 #include "hp_elem.h"
 
@@ -419,6 +420,90 @@ hipError_t hp_launch_hks_bsgs_presum(const HpLimb *limbs, u32 E, u32 n, u32 P, u
     const u32 tiles = (giants + HKS_PRE_GT - 1) / HKS_PRE_GT;
     return elem_launch_cw(k_hks_bsgs_presum<HKS_PRE_GT>, HKS_LT_CHUNK, P * E * tiles, n, stream, limbs, E, giants, babies, n, ElemChunks{},
                           baby, baby_pstride, tab, dst_pstride, add_prev ? 1u : 0u);
+}
+
+// Key generation (hp_dev_hks_keygen, hp_dev_hks_keygen_rot): one streaming multiply-add per word of a key.  Row = (r * nd + d) * E + m;
+// the workgroup reads its chunk of NTT(e[r][d]) -- which the transform left in key[r][d][0][m], where the result goes -- of a[r][d][m]
+// (its own rows, or the words already in key[r][d][1][m]), of s_to[m] and, on the limbs of digit d only, of the source secret, and
+// writes both key rows:
+//   key[r][d][0][m] = (NTT(e) - a * s_to + (m in digit d) * (P mod q_m) * from_r[m]) * 2^64 mod q_m,   key[r][d][1][m] = a * 2^64 mod q_m
+// as CANONICAL residues, whatever representatives come in.  The transformed error word is any u64 (hehub's fold leaves up to 16 q at a
+// modulus far below its power of two): Barrett, below 2q for every 64-bit word.  a, s_to and from_r are below 2q: hp_mul_hybrid_lazy
+// (a product below 4q^2, q < 2^60) and the Harvey products by P mod q_m and by 2^64 mod q_m (the limb's own pair r64 / r64h) are below
+// 2q for any 64-bit operand, the lazy sums stay there, and one conditional subtraction ends each row.
+// A thread reads every word of key[..][0] and key[..][1] before it writes it: no scratch copy of the error rows, a may be in place.
+// Traffic: e, a and the two key rows are streamed (non-temporal, 16 bytes per lane); s_to[m] is shared by the R * nd rows of its
+// modulus and is left to the caches.  ROT: from_r = move_r(s_to), read through the rotation's map (or, the involution, the 16 bytes
+// at n - 2 - i swapped) as k_hks_inner_hoisted reads its digit rows -- the row is s_to[m] again, so the scattered reads hit what the
+// whole launch keeps in cache; otherwise s_from[r][m], read once per call: streamed.
+template <bool ROT>
+__global__ void __launch_bounds__(ELEM_THREADS) k_hks_keygen(const HpLimb *__restrict__ limbs, const HpHksConsts *__restrict__ hc, u32 n,
+                                                           u32 chunks, const u64 *__restrict__ s_to, const u64 *__restrict__ s_from,
+                                                           HpKeygenMaps maps, const u64 *a, u64 *keys) {   // a may be NULL: in place
+    const u32 L = hc->L, E = hc->E, nd = hc->nd, alpha = hc->alpha;
+    const ElemTile tile(n, chunks);   // row = (r * nd + d) * E + m
+    const u32 m = tile.row % E, rd = tile.row / E, d = rd % nd, r = rd / nd;
+    const HpLimb lm = limbs[m];
+    const bool own = m < L && m / alpha == d;   // the message term: the limbs of digit d
+    const u64 pm = own ? hc->p_mod_q[m] : 0, pmh = own ? hc->p_mod_q_h[m] : 0;
+    u64 *k0 = keys + ((size_t)rd * 2 * E + m) * n, *k1 = k0 + (size_t)E * n;
+    const u64 *ar = a ? a + (size_t)tile.row * n : k1;
+    const u64 *st = s_to + (size_t)m * n;
+    const u64 *sf = ROT ? st : s_from + ((size_t)r * E + m) * n;
+    const u32 *__restrict__ map = ROT ? maps.map[r] : nullptr;   // ROT, NULL: the involution i -> n - 1 - i
+    const auto from = [&](u32 i) {
+        if (!own) return U2{0, 0};
+        if (!ROT) return ld_nt(sf + i);
+        if (map) {
+            const uint2 j = *reinterpret_cast<const uint2 *>(map + i);
+            return U2{sf[j.x], sf[j.y]};
+        }
+        const U2 v = *reinterpret_cast<const U2 *>(sf + (n - 2 - i));
+        return U2{v.y, v.x};
+    };
+    const auto word = [&](u64 e, u64 av, u64 sv, u64 fv, u64 &o0, u64 &o1) {
+        u64 b = hp_sub_lazy(hp_barrett_lazy(e, lm.q, lm.barrett_c), hp_mul_hybrid_lazy(av, sv, lm), lm.two_q);
+        if (own) b = hp_add_lazy(b, hp_harvey_lazy(fv, pm, pmh, lm.q), lm.two_q);
+        o0 = hp_strict(hp_harvey_lazy(b, lm.r64, lm.r64h, lm.q), lm.q);
+        o1 = hp_strict(hp_harvey_lazy(av, lm.r64, lm.r64h, lm.q), lm.q);
+    };
+    const auto pairs = tile.pairs();
+    if (tile.full()) {   // all loads of a thread first, then the arithmetic and the stores (hp_elem.h)
+        const size_t o = elem_full2(tile, 0);
+        U2 ve[ELEM_IT2], va[ELEM_IT2], vs[ELEM_IT2], vf[ELEM_IT2];
+#pragma unroll
+        for (int t = 0; t < ELEM_IT2; ++t) {
+            ve[t] = ld_nt(k0 + o + t * ELEM_STEP2);
+            va[t] = ld_nt(ar + o + t * ELEM_STEP2);
+            vs[t] = *reinterpret_cast<const U2 *>(st + o + t * ELEM_STEP2);
+            vf[t] = from((u32)(o + t * ELEM_STEP2));
+        }
+#pragma unroll
+        for (int t = 0; t < ELEM_IT2; ++t) {
+            U2 o0, o1;
+            word(ve[t].x, va[t].x, vs[t].x, vf[t].x, o0.x, o1.x);
+            word(ve[t].y, va[t].y, vs[t].y, vf[t].y, o0.y, o1.y);
+            st_nt(k0 + o + t * ELEM_STEP2, o0);
+            st_nt(k1 + o + t * ELEM_STEP2, o1);
+        }
+        return;
+    }
+    for (const u32 i : pairs) {   // a row shorter than a chunk (n is even: always whole pairs)
+        const U2 e = ld_nt(k0 + i), av = ld_nt(ar + i), sv = *reinterpret_cast<const U2 *>(st + i), fv = from(i);
+        U2 o0, o1;
+        word(e.x, av.x, sv.x, fv.x, o0.x, o1.x);
+        word(e.y, av.y, sv.y, fv.y, o0.y, o1.y);
+        st_nt(k0 + i, o0);
+        st_nt(k1 + i, o1);
+    }
+}
+
+hipError_t hp_launch_hks_keygen(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 nd, u32 n, u32 R, const u64 *s_to, const u64 *s_from,
+                                const HpKeygenMaps *maps, const u64 *a, u64 *keys, hipStream_t stream) {
+    if (R == 0) return hipSuccess;
+    if (maps && R > HP_HOIST_TABLE_MAX) return hipErrorInvalidValue;
+    if (maps) return elem_launch(k_hks_keygen<true>, R * nd * E, n, stream, limbs, hc, n, ElemChunks{}, s_to, s_from, *maps, a, keys);
+    return elem_launch(k_hks_keygen<false>, R * nd * E, n, stream, limbs, hc, n, ElemChunks{}, s_to, s_from, HpKeygenMaps{}, a, keys);
 }
 
 // ModDown conversion: Garner digits of the special-prime part once per coefficient, then its exact centred value

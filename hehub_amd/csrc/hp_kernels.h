@@ -184,6 +184,9 @@ hipError_t hp_launch_base_to_single_crt(const HpLimb *limbs, const HpCrtConsts *
 // noise [P][n] (int64) -> out rows p*out_pstride + k: the per-modulus lift of sampling.cpp:77-83
 hipError_t hp_launch_lift_noise(const HpLimb *limbs, u32 L, u32 n, u32 P, const long long *noise, u64 *out, u32 out_pstride,
                                 hipStream_t stream);
+// coeffs [P][n] (any int64) -> out rows p*out_pstride + k: the strict residue of every coefficient in every modulus
+hipError_t hp_launch_spread_signed(const HpLimb *limbs, u32 L, u32 n, u32 P, const long long *coeffs, u64 *out, u32 out_pstride,
+                                   hipStream_t stream);
 // ct[p][0] holds NTT(lift(noise)) on entry; c1, ptn [P][L][n], sk [L][n] -> ct [P][2][L][n]   (rlwe.cpp:52,70)
 hipError_t hp_launch_enc_fin(const HpLimb *limbs, u32 L, u32 n, u32 P, const u64 *c1, const u64 *sk, const u64 *ptn, u64 *ct,
                              hipStream_t stream);
@@ -263,6 +266,15 @@ struct HpPreTable {
 };
 hipError_t hp_launch_hks_bsgs_presum(const HpLimb *limbs, u32 E, u32 n, u32 P, u32 giants, u32 babies, const u64 *baby, size_t baby_pstride,
                                      const HpPreTable &tab, size_t dst_pstride, bool add_prev, hipStream_t stream);
+// key generation (hp_dev_hks_keygen / _rot): keys [R][nd][2][E][n] with NTT(e[r][d]) in keys[r][d][0] on entry (any u64 words) ->
+//   keys[r][d][0][m] = (NTT(e) - a[r][d][m] * s_to[m] + (m in digit d) * (P mod q_m) * from_r[m]) * 2^64,  keys[r][d][1][m] = a * 2^64,
+// canonical residues.  a [R][nd][E][n], or NULL: the rows already in keys[r][d][1].  from_r = s_from [R][E][n] (maps == NULL), or
+// s_to itself read through maps->map[r] (a cycle map of the context's cache; NULL: the involution), R <= HP_HOIST_TABLE_MAX then
+struct HpKeygenMaps {
+    const u32 *map[HP_HOIST_TABLE_MAX];
+};
+hipError_t hp_launch_hks_keygen(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 nd, u32 n, u32 R, const u64 *s_to, const u64 *s_from,
+                                const HpKeygenMaps *maps, const u64 *a, u64 *keys, hipStream_t stream);
 // merged ModDown + rescale (hp_engine.cpp: hks_mult): rem[p2][i] += (P mod q_i) * centre(c_last[p2]) for i < L-1, in the
 // coefficient domain; c_last = strict coefficients modulo q_{L-1} of the relinearised limb L-1
 hipError_t hp_launch_hks_combine(const HpLimb *limbs, const HpHksConsts *hc, u32 L, u32 n, u32 P2, const u64 *clast, u64 *rem,

@@ -508,6 +508,45 @@ class Engine:
                                                               self._ptr(ct1), self._ptr(ct2), self._ptr(key), self._ptr(out)))
         return out
 
+    def poly_from_signed(self, moduli, coeffs):
+        """small signed polynomials, coeffs [B][n] (any int64 values, device tensor) -> NTT form [B][L][n]: the words hp_dev_ntt produces
+        from the strict residues.  How a ternary secret or an error polynomial gets to the device."""
+        B, n = coeffs.shape
+        L = len(moduli)
+        out = self.empty((B, L, n))
+        self._chk(self.lib.hp_dev_poly_from_signed(self.h, n.bit_length() - 1, L, _u64arr(moduli), B, self._ptr(coeffs), self._ptr(out)))
+        return out
+
+    def hks_keygen(self, moduli_ext, k: int, alpha: int, s_to, s_from, a, e, out=None):
+        """hybrid keys on the device: s_to [E][n], s_from [R][E][n], the uniform rows a [R][dnum][E][n] (NTT form, words < 2q) and the error
+        polynomials e [R][dnum][n] (int64 coefficients) -> [R][dnum][2][E][n], canonical words.  a = None: the rows already lie in
+        out[r][d][1] and are converted in place."""
+        R, nd, n = e.shape
+        E = len(moduli_ext)
+        if out is None:
+            if a is None:
+                raise InvalidArgument(capi.HP_EINVAL, "hks_keygen: a = None needs the rows in out[..][1]")
+            out = self.empty((R, nd, 2, E, n))
+        self._chk(self.lib.hp_dev_hks_keygen(self.h, n.bit_length() - 1, E - k, k, alpha, _u64arr(moduli_ext), R, self._ptr(s_to),
+                                             self._ptr(s_from), None if a is None else self._ptr(a), self._ptr(e), self._ptr(out)))
+        return out
+
+    def hks_keygen_rot(self, moduli_ext, k: int, alpha: int, s, steps, a, e, conj=None, out=None):
+        """rotation / conjugation keys for the secret s [E][n]: key r switches move_r(s) back to s, move_r the cycle by steps[r] or (where
+        conj[r]) the involution -- the key the rotate calls take for that entry.  a, e, out as for hks_keygen."""
+        R, nd, n = e.shape
+        E = len(moduli_ext)
+        assert len(steps) == R and (conj is None or len(conj) == R)
+        if out is None:
+            if a is None:
+                raise InvalidArgument(capi.HP_EINVAL, "hks_keygen_rot: a = None needs the rows in out[..][1]")
+            out = self.empty((R, nd, 2, E, n))
+        st = (C.c_size_t * R)(*[int(x) for x in steps])
+        cj = (C.c_ubyte * R)(*[1 if c else 0 for c in conj]) if conj is not None else None
+        self._chk(self.lib.hp_dev_hks_keygen_rot(self.h, n.bit_length() - 1, E - k, k, alpha, _u64arr(moduli_ext), R, st, cj, self._ptr(s),
+                                                 None if a is None else self._ptr(a), self._ptr(e), self._ptr(out)))
+        return out
+
     def ckks_rescale_n(self, moduli, ct, drops: int):
         B, _, L, n = ct.shape
         out = self.empty((B, 2, L - drops, n))

@@ -574,6 +574,42 @@ int hp_dev_ckks_lintrans_bsgs_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, 
 int hp_dev_ckks_mult_relin_rescale_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha,
                                        const uint64_t *moduli_ext, size_t batch, const uint64_t *d_ct1,
                                        const uint64_t *d_ct2, const uint64_t *d_key, uint64_t *d_out);
+/* Hybrid keys generated on the device.  Sampling stays with the caller: the uniform rows a and the error polynomials e are INPUTS, so
+ * a call is deterministic and every output word is pinned by the exact model (tests/test_gpu_hks_keygen.py); what runs here is the
+ * arithmetic -- residues of small signed polynomials, batched forward transforms, one streaming multiply-add in Montgomery form.
+ * None of the three calls needs workspace: the error rows are spread into d_keys[r][d][0] and transformed there in place.
+ *
+ * hp_dev_poly_from_signed: small signed polynomials -> NTT form.  Coefficient i of polynomial b as a strict residue of every modulus
+ * (a negative c maps to q_m - (|c| mod q_m), to 0 when that is q_m; defined for every int64_t, INT64_MIN included), then the forward
+ * transform: row [b][m] holds the words hp_dev_ntt produces from those residues.  How a ternary secret or an error polynomial gets
+ * to the device.  HP_EINVAL: L == 0 or L > 32, batch == 0, a pointer that is NULL or not 16-byte aligned, d_out overlapping d_coeffs. */
+int hp_dev_poly_from_signed(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, size_t batch,
+                            const int64_t *d_coeffs /* i64[batch][N] */, uint64_t *d_out /* u64[batch][L][N] */);
+/* hp_dev_hks_keygen: `keys` keys u64[dnum][2][L+k][N] for hp_dev_hks_switch and every call built on it.  With P = p_0...p_{k-1},
+ * E = L + k, dnum = ceil(L / alpha) and digit d = the limbs d*alpha .. min((d+1)*alpha, L) - 1, for key r, digit d, modulus m < E:
+ *     b[m]            = NTT(e[r][d])[m] - a[r][d][m] * s_to[m] + (m in digit d) * (P mod q_m) * s_from[r][m]      (mod q_m)
+ *     key[r][d][0][m] = b[m]       * 2^64 mod q_m
+ *     key[r][d][1][m] = a[r][d][m] * 2^64 mod q_m
+ * Every output word is the CANONICAL residue (< q_m) at either parity level: the words of keygen() in tests/hks_model.py given the same
+ * a and e.  The key switches a polynomial under s_from to s_to; a relinearisation key is s_from = s * s (hp_dev_poly_mul).
+ * d_a == NULL: row a[r][d] already lies, in plain form, in d_keys[r][d][1] and is converted to Montgomery form in place (a key set
+ * then needs no second buffer of half its size).
+ * HP_EINVAL before anything is enqueued: the limits of hp_dev_hks_switch, keys == 0, a NULL pointer (d_a excepted), a pointer that is
+ * not 16-byte aligned, d_keys overlapping any input.  Chains that hp_dev_hks_switch refuses are refused with its code. */
+int hp_dev_hks_keygen(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t keys,
+                      const uint64_t *d_s_to,    /* u64[L+k][N]        NTT form, words < 2 * modulus            */
+                      const uint64_t *d_s_from,  /* u64[keys][L+k][N]  NTT form, words < 2 * modulus; only the limbs < L are read */
+                      const uint64_t *d_a,       /* u64[keys][dnum][L+k][N] uniform rows, NTT form, words < 2 * modulus; may be NULL */
+                      const int64_t *d_e,        /* i64[keys][dnum][N] error polynomials, coefficient domain    */
+                      uint64_t *d_keys);         /* u64[keys][dnum][2][L+k][N]                                  */
+/* hp_dev_hks_keygen_rot: rotation / conjugation keys -- the same call with s_to = s and s_from[r] = move_r(s), move_r being
+ * hp_dev_poly_involution where conj[r] != 0 and hp_dev_poly_cycle by steps[r] otherwise: key r is the one the rotate entry points take
+ * for that entry.  steps and conj are HOST arrays as for hp_dev_ckks_rotate_hoisted_hks (conj may be NULL; a conjugation ignores its
+ * step).  The moved secret is read through the automorphism's index map inside the kernel, never materialised.
+ * HP_EINVAL as for hp_dev_hks_keygen, and for a step >= 2^17 on an entry that is not a conjugation. */
+int hp_dev_hks_keygen_rot(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t keys,
+                          const size_t *steps, const unsigned char *conj, const uint64_t *d_s /* u64[L+k][N] */,
+                          const uint64_t *d_a, const int64_t *d_e, uint64_t *d_keys);
 /* ct u64[batch][2][L][N] -> out u64[batch][2][L-drops][N]; d_tmp: 2 * batch*2*(L-1)*N words (may be NULL for drops == 1) */
 int hp_dev_ckks_rescale_n(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, size_t drops, size_t batch,
                           const uint64_t *d_ct, uint64_t *d_tmp, uint64_t *d_out);
