@@ -541,30 +541,20 @@ extern "C" int hp_dev_ckks_lintrans_bsgs_hks(hp_ctx *ctx, size_t logn, size_t L,
     return c.finish(batch, {acc, yp, rem}, Addend(), out);                                                      // stage 7
 }
 
-// ckks::mult_low_level + relinearisation with a hybrid key + rescale by the last ciphertext modulus
-extern "C" int hp_dev_ckks_mult_relin_rescale_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
-                                       size_t batch, const uint64_t *ct1, const uint64_t *ct2, const uint64_t *key,
-                                       uint64_t *out) {
-    HP_ENTER(ctx);
-    HP_REQUIRE(ctx, moduli_ext, ct1, ct2, key, out);
-    HP_ALIGNED(ctx, ct1, ct2, key, out);
-    HksCall c(ctx, logn, L, k, alpha, moduli_ext, batch);
-    if (c.rc) return c.rc;
-    if (L < 2) return fail(ctx, HP_EINVAL, "Unable to drop the only one prime.");
-    if (c.open()) return c.rc;
+// What follows the tensor product of a hybrid multiplication, on an open call: hybrid relinearisation of d2, + (d0, d1), rescale by the
+// last ciphertext modulus.  quad [batch][3][L][N], words below 2q: the workspace block of hp_dev_ckks_mult_relin_rescale_hks and
+// hp_dev_ckks_dot_relin_rescale_hks, the caller's memory in hp_dev_ckks_relin_rescale_hks -> out [batch][2][L-1][N].  Everything here
+// is linear in quad, which is why a sum of products pays it once.
+static size_t relin_rescale_words(const HksCall &c, size_t batch) {
+    return padded(batch * 2 * c.L * c.n) / 8 + c.switch_words(batch) + drop_ws_words(c.n, c.L, 2 * batch) + 2 * (padded(2 * batch * c.n) / 8);
+}
+static int relin_rescale(const HksCall &c, size_t batch, const u64 *quad, const u64 *key, u64 *out, Carver &cv) {
+    hp_ctx *ctx = c.ctx;
     const Plan *plan = c.plan;
-    const size_t n = c.n;
-    const size_t words = padded(batch * 3 * L * n) / 8 + padded(batch * 2 * L * n) / 8 + c.switch_words(batch) +
-                         drop_ws_words(n, L, 2 * batch) + 2 * (padded(2 * batch * n) / 8);
-    int rc = ws_reserve(ctx, words * 8);
-    if (rc) return rc;
-    Carver cv(ctx->ws);
-    u64 *quad = cv.take(batch * 3 * L * n), *lin = cv.take(batch * 2 * L * n);
-    {
-        ProfScope ps(ctx, "tensor");
-        if ((rc = chk(ctx, hp_launch_tensor(plan->d_limbs, (u32)L, 0, (u32)L, (u32)n, (u32)batch, ct1, ct2, quad, ctx->stream), "tensor")))
-            return rc;
-    }
+    const uint64_t *moduli_ext = c.mext;
+    const size_t logn = c.logn, L = c.L, n = c.n;
+    int rc;
+    u64 *lin = cv.take(batch * 2 * L * n);
     if (fused_drop_ok(ctx, logn) && !ctx->hks_two_step) {
         // ModDown and the rescale in ONE transform per remaining limb.  With c = the coefficients of the relinearised limb L-1,
         //   ((ks_i - NTT(rem_i)) P^-1 + quad_i - NTT(centre_i(c))) q_last^-1 = ((ks_i - NTT(rem_i + P centre_i(c))) P^-1 + quad_i) q_last^-1
@@ -608,6 +598,129 @@ extern "C" int hp_dev_ckks_mult_relin_rescale_hks(hp_ctx *ctx, size_t logn, size
     }
     if ((rc = c.key_switch(batch, quad + 2 * L * n, 3 * L, key, Addend(quad, L, 3 * L, 3), lin, cv))) return rc;
     return drop_last(ctx, plan, logn, L, 2 * batch, false, 0, lin, Addend(), out, cv);
+}
+
+// ckks::mult_low_level + relinearisation with a hybrid key + rescale by the last ciphertext modulus
+extern "C" int hp_dev_ckks_mult_relin_rescale_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                       size_t batch, const uint64_t *ct1, const uint64_t *ct2, const uint64_t *key,
+                                       uint64_t *out) {
+    HP_ENTER(ctx);
+    HP_REQUIRE(ctx, moduli_ext, ct1, ct2, key, out);
+    HP_ALIGNED(ctx, ct1, ct2, key, out);
+    HksCall c(ctx, logn, L, k, alpha, moduli_ext, batch);
+    if (c.rc) return c.rc;
+    if (L < 2) return fail(ctx, HP_EINVAL, "Unable to drop the only one prime.");
+    if (c.open()) return c.rc;
+    const size_t n = c.n;
+    int rc = ws_reserve(ctx, (padded(batch * 3 * L * n) / 8 + relin_rescale_words(c, batch)) * 8);
+    if (rc) return rc;
+    Carver cv(ctx->ws);
+    u64 *quad = cv.take(batch * 3 * L * n);
+    {
+        ProfScope ps(ctx, "tensor");
+        if ((rc = chk(ctx, hp_launch_tensor(c.plan->d_limbs, (u32)L, 0, (u32)L, (u32)n, (u32)batch, ct1, ct2, quad, ctx->stream), "tensor")))
+            return rc;
+    }
+    return relin_rescale(c, batch, quad, key, out, cv);
+}
+
+// the tail alone, on the caller's quadratic ciphertexts (hp_dev_mult_low_level's or hp_dev_ckks_tensor_sum's)
+extern "C" int hp_dev_ckks_relin_rescale_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                             size_t batch, const uint64_t *d_quad, const uint64_t *d_key, uint64_t *d_out) {
+    HP_ENTER(ctx);
+    HP_REQUIRE(ctx, moduli_ext, d_quad, d_key, d_out);
+    HP_ALIGNED(ctx, d_quad, d_key, d_out);
+    HksCall c(ctx, logn, L, k, alpha, moduli_ext, batch);
+    if (c.rc) return c.rc;
+    if (L < 2) return fail(ctx, HP_EINVAL, "Unable to drop the only one prime.");
+    int rc = no_overlap(ctx, "relin_rescale", d_quad, batch * 3 * L * c.n * 8, d_out, batch * 2 * (L - 1) * c.n * 8);
+    if (rc) return rc;
+    if (c.open()) return c.rc;
+    if ((rc = ws_reserve(ctx, relin_rescale_words(c, batch) * 8))) return rc;
+    Carver cv(ctx->ws);
+    return relin_rescale(c, batch, d_quad, d_key, d_out, cv);
+}
+
+// ---- sums of products: lazy relinearisation ----------------------------------------------------------------------------------------
+// rescale(relin(sum_t a_t (x) b_t)) = rescale(sum_t (d0_t, d1_t) + switch(sum_t d2_t)), residue for residue: T products pay one switch
+// and one rounding.  The quadratic sum is one streaming kernel (k_tensor_sum, hp_ks.hip), one launch per argument table.
+struct TensorSumTerms {
+    size_t terms;
+    const uint64_t *const *a, *const *b;   // HOST arrays of device addresses, each u64[batch][2][L][N]
+};
+// before anything is enqueued: the list itself, and `out` (the call's output, out_bytes long) against every operand
+static int tensor_sum_ok(hp_ctx *ctx, const char *call, size_t n, size_t L, size_t batch, const TensorSumTerms &ts, const void *out,
+                         size_t out_bytes) {
+    const auto bad = [&](const char *what) { return fail(ctx, HP_EINVAL, std::string(call) + ": " + what); };
+    if (ts.terms == 0) return bad("no terms");
+    // (512 words per workgroup at the least: every launch stays below 2^30 workgroups, and every u32 row count with it)
+    if (batch > ((size_t)1 << 30) / (L * ((n + 511) / 512)))
+        return fail(ctx, HP_EUNSUPPORTED, std::string(call) + ": too many ciphertexts for one call");
+    const size_t in_bytes = batch * 2 * L * n * 8;
+    const uintptr_t o0 = (uintptr_t)out;
+    for (size_t t = 0; t < ts.terms; t++)
+        for (const uint64_t *p : {ts.a[t], ts.b[t]}) {
+            if (!p || ((uintptr_t)p & 15u)) return bad("NULL or misaligned operand");
+            if (o0 < (uintptr_t)p + in_bytes && (uintptr_t)p < o0 + out_bytes) return bad("the output overlaps an operand");
+        }
+    return HP_OK;
+}
+// quad [batch][3][L][N] = the sum over the list, `pass` terms per launch (tensor_sum_max_terms' answer)
+static int tensor_sum(hp_ctx *ctx, const HpLimb *limbs, size_t n, size_t L, size_t batch, size_t pass, const TensorSumTerms &ts, u64 *quad) {
+    for (size_t t0 = 0; t0 < ts.terms; t0 += pass) {
+        HpTensorSumTable tab;
+        memset(&tab, 0, sizeof(tab));
+        tab.terms = (u32)std::min(pass, ts.terms - t0);
+        std::copy(ts.a + t0, ts.a + t0 + tab.terms, tab.a);
+        std::copy(ts.b + t0, ts.b + t0 + tab.terms, tab.b);
+        ProfScope ps(ctx, "tensor");
+        int rc = chk(ctx, hp_launch_tensor_sum(limbs, (u32)L, (u32)n, (u32)batch, tab, t0 != 0, quad, ctx->stream), "tensor_sum");
+        if (rc) return rc;
+    }
+    return HP_OK;
+}
+
+extern "C" int hp_dev_ckks_tensor_sum(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, size_t batch, size_t terms,
+                                      const uint64_t *const *d_a, const uint64_t *const *d_b, uint64_t *d_quad) {
+    HP_ENTER(ctx);
+    HP_REQUIRE(ctx, moduli, d_a, d_b, d_quad);
+    HP_ALIGNED(ctx, d_quad);
+    if (!logn_ok(logn)) return fail(ctx, HP_EUNSUPPORTED, HP_LOGN_MSG);
+    if (L < 1 || L > HP_MAX_LIMBS) return fail(ctx, HP_EINVAL, "unsupported number of moduli");
+    if (batch == 0) return fail(ctx, HP_EINVAL, "empty batch");
+    const size_t n = (size_t)1 << logn;
+    const TensorSumTerms ts = {terms, d_a, d_b};
+    int rc = tensor_sum_ok(ctx, "tensor_sum", n, L, batch, ts, d_quad, batch * 3 * L * n * 8);
+    if (rc) return rc;
+    const size_t pass = tensor_sum_max_terms(moduli, L, HP_TENSOR_SUM_MAX);   // terms per launch
+    if (pass == 0) return fail(ctx, HP_EUNSUPPORTED, "tensor_sum: moduli too large for the 128-bit accumulators");
+    const Plan *plan;
+    if ((rc = get_plan(ctx, 0, moduli, L, false, &plan))) return rc;
+    return tensor_sum(ctx, plan->d_limbs, n, L, batch, pass, ts, d_quad);
+}
+
+// the composition: the sum into a workspace quad, then the tail.  One reservation, a function of the shape alone, never of `terms`
+extern "C" int hp_dev_ckks_dot_relin_rescale_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                                 size_t batch, size_t terms, const uint64_t *const *d_a, const uint64_t *const *d_b,
+                                                 const uint64_t *d_key, uint64_t *d_out) {
+    HP_ENTER(ctx);
+    HP_REQUIRE(ctx, moduli_ext, d_a, d_b, d_key, d_out);
+    HP_ALIGNED(ctx, d_key, d_out);
+    HksCall c(ctx, logn, L, k, alpha, moduli_ext, batch);
+    if (c.rc) return c.rc;
+    if (L < 2) return fail(ctx, HP_EINVAL, "Unable to drop the only one prime.");
+    const size_t n = c.n;
+    const TensorSumTerms ts = {terms, d_a, d_b};
+    int rc = tensor_sum_ok(ctx, "dot_relin_rescale", n, L, batch, ts, d_out, batch * 2 * (L - 1) * n * 8);
+    if (rc) return rc;
+    const size_t pass = tensor_sum_max_terms(moduli_ext, L, HP_TENSOR_SUM_MAX);
+    if (pass == 0) return fail(ctx, HP_EUNSUPPORTED, "dot_relin_rescale: moduli too large for the 128-bit accumulators");
+    if (c.open()) return c.rc;
+    if ((rc = ws_reserve(ctx, (padded(batch * 3 * L * n) / 8 + relin_rescale_words(c, batch)) * 8))) return rc;
+    Carver cv(ctx->ws);
+    u64 *quad = cv.take(batch * 3 * L * n);
+    if ((rc = tensor_sum(ctx, c.plan->d_limbs, n, L, batch, pass, ts, quad))) return rc;
+    return relin_rescale(c, batch, quad, d_key, d_out, cv);
 }
 
 // ---- key generation ----------------------------------------------------------------------------------------------------------------

@@ -154,6 +154,16 @@ size_t hks_lintrans_max_rotations(const u64 *mext, size_t E, size_t nd, size_t t
     return r < table_max ? (size_t)r : table_max;
 }
 
+size_t tensor_sum_max_terms(const u64 *moduli, size_t L, size_t table_max) {
+    typedef unsigned __int128 u128;
+    u64 q = 0;
+    for (size_t m = 0; m < L; m++) q = std::max(q, moduli[m]);
+    if (q == 0 || q >> 62) return 0;   // (2q must leave room in a word; (2q - 1)^2 then stays below 2^126)
+    const u128 w = 2 * (u128)q - 1, top = ((((u128)1 << 64) - q) << 64) - 1;
+    const u128 r = top / (2 * w * w);
+    return r < table_max ? (size_t)r : table_max;
+}
+
 bool hks_bsgs_plan(const u64 *mext, size_t n, size_t L, size_t k, size_t alpha, size_t batch, size_t babies, size_t giants,
                    HksBsgsPlan &out) {
     out = HksBsgsPlan();

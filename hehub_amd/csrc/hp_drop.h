@@ -146,6 +146,12 @@ bool hks_limb_consts(const u64 *mext, size_t L, size_t k, HksLimbConsts &out);  
 // products of lazy words, plus the folded c0 term) is below w = 4 nd ceil(q^2 / 2^64) + 3q, which must be a 64-bit word, and a
 // diagonal word below 2q: the largest R with R w 2q < 2^128.  Exact integers.
 size_t hks_lintrans_max_rotations(const u64 *mext, size_t E, size_t nd, size_t table_max);
+// How many terms one launch of k_tensor_sum (hp_ks.hip) may sum, at most table_max; 0: not even one.  With q the largest modulus
+// of the chain, operand words at most 2q - 1 and the d1 column with two products per term, T terms sum to at most 2 T (2q - 1)^2.
+// The Montgomery step returns hi + mulhi(u, q) + 1 in a 64-bit word, so the high word of the sum must stay at most 2^64 - 1 - q:
+//   q == 0 or q >= 2^62: 0;  else min(table_max, floor(((2^64 - q) 2^64 - 1) / (2 (2q - 1)^2)))
+// -- the whole table of 32 for every modulus the transforms accept (below 2^59.5), 30 at q = 2^60.  Exact integers.
+size_t tensor_sum_max_terms(const u64 *moduli, size_t L, size_t table_max);
 // The pass plan and the workspace of hp_dev_ckks_lintrans_bsgs_hks (hp_api_hks.cpp), a function of the shape alone -- never of the
 // steps or of which diagonals are present.  With E = L + k, nd = ceil(L / alpha), pad(w) = w words rounded up to 256 bytes:
 //   baby_pass     babies per pre-sum launch (and per baby-stage launch): hks_lintrans_max_rotations(mext, E, nd, HP_BSGS_TABLE_MAX) --

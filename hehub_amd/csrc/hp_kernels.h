@@ -128,6 +128,18 @@ struct HpTensorRows {
 };
 hipError_t hp_launch_tensor_rows(const HpLimb *limbs, u32 L, u32 k_first, u32 kc, u32 n, u32 P, const HpTensorRows &rows, u64 *quad,
                                  hipStream_t stream);
+// sum of tensor products (hp_dev_ckks_tensor_sum): term t = the ciphertext batches a[t], b[t], each [P][2][L][n] with words below
+// 2 * modulus  -> quad [P][3][L][n] = (sum a0 b0, sum (a0 b1 + a1 b0), sum a1 b1), words below 2 * modulus; add_prev: added to the
+// words quad already holds (the launches after the first of a long list).  The addresses travel as kernel arguments.
+// terms <= hpi::tensor_sum_max_terms (hp_drop.h): the 128-bit accumulators must stay within the Montgomery step's range
+#define HP_TENSOR_SUM_MAX 32
+struct HpTensorSumTable {
+    const u64 *a[HP_TENSOR_SUM_MAX];
+    const u64 *b[HP_TENSOR_SUM_MAX];
+    u32 terms;
+};
+hipError_t hp_launch_tensor_sum(const HpLimb *limbs, u32 L, u32 n, u32 P, const HpTensorSumTable &tab, bool add_prev, u64 *quad,
+                                hipStream_t stream);
 // rgsw.cpp:121-153: digits [P][L][L+1][n] (diagonal taken from pt [P][L][n]), key [L][2][L+1][n]
 //   -> out [P][2][L+1][n]
 // only output moduli [k_first, k_first + kc) of the L+1 are computed (kc = L+1: all)

@@ -69,6 +69,83 @@ hipError_t hp_launch_tensor_rows(const HpLimb *limbs, u32 L, u32 k_first, u32 kc
                           rows, quad);
 }
 
+// ---- sum of tensor products (hp_dev_ckks_tensor_sum) ------------------------------------------
+// quad = (sum_t a0 b0, sum_t (a0 b1 + a1 b0), sum_t a1 b1) over the terms of the table, for lazy relinearisation: everything after the
+// tensor product is linear in the quadratic ciphertext, so T products pay ONE key switch.  A thread owns one pair of words of a row
+// (p, limb), as in k_tensor, and keeps them for every term: six carry-save accumulators (three outputs x two words), per term four
+// 16-byte non-temporal loads (every operand word is read once per call) and four hp_mac2, and after the last term ONE Montgomery
+// reduction per output word.  The operands are plain words, so that reduction leaves a factor 2^-64: undone by the Harvey
+// multiplication by 2^64 mod q with the limb's own pair (r64, r64h) -- the tail of k_hks_inner_lintrans (hp_hks.hip): below 2q for any
+// 64-bit input, no new constant.  HBM traffic per output word: 32 T + 24 bytes, against (56 + 24 + 24) T for T launches of k_tensor
+// and a fold of their rows.
+// Range: operand words below 2q, the d1 column with two products per term: a launch of T terms sums at most 2 T (2q - 1)^2, and the
+// Montgomery step returns hi + mulhi(u, q) + 1, so hi must stay at most 2^64 - 1 - q: the host keeps T within that
+// (hpi::tensor_sum_max_terms, hp_drop.h: the whole table for every modulus the transforms accept).  A larger operand word can wrap
+// the sums unnoticed.  A longer list takes one launch per table; a later launch adds its reduced word to the word the earlier one left
+// (add_prev) -- the contract is on residues, so the intermediate reductions are free.
+// TWO: the lane's words i, i + 1 (16-byte accesses); else the single last word of an odd row
+template <bool TWO>
+HP_DEV void tensor_sum_words(const HpLimb &m, const HpTensorSumTable &tab, size_t at, size_t poly, u32 add_prev, u64 *d0) {
+    HpAcc s[3][2];   // [output][word]
+#pragma unroll
+    for (int c = 0; c < 3; c++) { hp_acc_zero(s[c][0]); hp_acc_zero(s[c][1]); }
+    for (u32 t = 0; t < tab.terms; t++) {
+        const u64 *a0 = tab.a[t] + at, *b0 = tab.b[t] + at;
+        U2 va0, va1, vb0, vb1;
+        if (TWO) {
+            va0 = ld_nt(a0); va1 = ld_nt(a0 + poly);
+            vb0 = ld_nt(b0); vb1 = ld_nt(b0 + poly);
+        } else {
+            va0 = U2{a0[0], 0}; va1 = U2{a0[poly], 0};
+            vb0 = U2{b0[0], 0}; vb1 = U2{b0[poly], 0};
+        }
+        hp_mac2(s[0][0], va0.x, vb0.x, s[0][1], va0.y, vb0.y);
+        hp_mac2(s[1][0], va0.x, vb1.x, s[1][1], va0.y, vb1.y);
+        hp_mac2(s[1][0], va1.x, vb0.x, s[1][1], va1.y, vb0.y);
+        hp_mac2(s[2][0], va1.x, vb1.x, s[2][1], va1.y, vb1.y);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        u64 *dst = d0 + (size_t)c * poly;
+        U2 v = acc2_montgomery(s[c][0], s[c][1], m.q, m.mqinv);   // the sum * 2^-64 ...
+        v.x = hp_harvey_lazy(v.x, m.r64, m.r64h, m.q);            // ... * 2^64, below 2q
+        v.y = hp_harvey_lazy(v.y, m.r64, m.r64h, m.q);
+        if (TWO) {
+            if (add_prev) {
+                const U2 old = *reinterpret_cast<const U2 *>(dst);
+                v.x = hp_add_lazy(v.x, old.x, m.two_q);
+                v.y = hp_add_lazy(v.y, old.y, m.two_q);
+            }
+            st_nt(dst, v);
+        } else {
+            dst[0] = add_prev ? hp_add_lazy(v.x, dst[0], m.two_q) : v.x;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(ELEM_THREADS) k_tensor_sum(const HpLimb *__restrict__ limbs, u32 L, u32 n, u32 chunks, u32 cw,
+                                                            HpTensorSumTable tab, u32 add_prev, u64 *__restrict__ quad) {
+    const ElemTile tile(n, chunks, cw);   // row = p*L + k; cw = words per workgroup
+    const u32 p = tile.row / L, k = tile.row % L;
+    const HpLimb m = limbs[k];
+    const size_t poly = (size_t)L * n;
+    const size_t in = (size_t)p * 2 * poly + (size_t)k * n;   // row (p, polynomial 0, k) of every operand
+    u64 *d0 = quad + (size_t)p * 3 * poly + (size_t)k * n;
+    for (const u32 i : tile.pairs()) {
+        if (tile.pair(i)) tensor_sum_words<true>(m, tab, in + i, poly, add_prev, d0 + i);
+        else tensor_sum_words<false>(m, tab, in + i, poly, add_prev, d0 + i);
+    }
+}
+
+hipError_t hp_launch_tensor_sum(const HpLimb *limbs, u32 L, u32 n, u32 P, const HpTensorSumTable &tab, bool add_prev, u64 *quad,
+                                hipStream_t stream) {
+    if (P == 0 || L == 0 || tab.terms == 0) return hipSuccess;
+    if (tab.terms > HP_TENSOR_SUM_MAX) return hipErrorInvalidValue;
+    const u32 cw = tensor_chunk(n, P * L);
+    if ((u64)P * L * ((n + cw - 1) / cw) >= (1ull << 31)) return hipErrorInvalidValue;   // (workgroups of one launch)
+    return elem_launch_cw(k_tensor_sum, cw, P * L, n, stream, limbs, L, n, ElemChunks{}, cw, tab, add_prev ? 1u : 0u, quad);
+}
+
 // ---- key-switch inner product: rgsw.cpp:121-153 --------------------------------------------
 // out[p][half][k][i] = montgomery_128( sum_j D[p][j][k][i] * key[j][half][k][i] ), 128-bit accumulators
 // in registers, both halves from one pass over the digits.  Per (p, k, i): reads L digit words and 2L key

@@ -508,6 +508,41 @@ class Engine:
                                                               self._ptr(ct1), self._ptr(ct2), self._ptr(key), self._ptr(out)))
         return out
 
+    @staticmethod
+    def _terms(a_list, b_list):
+        """two lists of ciphertext batches [B][2][L][n] (device tensors) as ctypes arrays of addresses"""
+        T = len(a_list)
+        assert len(b_list) == T and T > 0
+        shape = a_list[0].shape
+        assert all(t.shape == shape and t.is_contiguous() and t.element_size() == 8 for t in list(a_list) + list(b_list))
+        return T, (capi.P * T)(*[t.data_ptr() for t in a_list]), (capi.P * T)(*[t.data_ptr() for t in b_list])
+
+    def ckks_tensor_sum(self, moduli, a_list, b_list, out=None):
+        """sum_t a_list[t] (x) b_list[t] for ciphertext batches [B][2][L][n] (device tensors anywhere; words below 2q) ->
+        the quadratic ciphertexts [B][3][L][n] in mult_low_level's layout, by one streaming kernel.  a_list may be b_list (squares)."""
+        B, _, L, n = a_list[0].shape
+        T, ap, bp = self._terms(a_list, b_list)
+        out = self.empty((B, 3, L, n)) if out is None else out
+        self._chk(self.lib.hp_dev_ckks_tensor_sum(self.h, n.bit_length() - 1, L, _u64arr(moduli), B, T, ap, bp, self._ptr(out)))
+        return out
+
+    def ckks_relin_rescale_hks(self, moduli_ext, k: int, alpha: int, quad, key, out=None):
+        """quad [B][3][L][n] (mult_low_level's or ckks_tensor_sum's) -> hybrid relinearisation + rescale, [B][2][L-1][n]"""
+        B, _, L, n = quad.shape
+        out = self.empty((B, 2, L - 1, n)) if out is None else out
+        self._chk(self.lib.hp_dev_ckks_relin_rescale_hks(self.h, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), B,
+                                                         self._ptr(quad), self._ptr(key), self._ptr(out)))
+        return out
+
+    def ckks_dot_hks(self, moduli_ext, k: int, alpha: int, a_list, b_list, key, out=None):
+        """rescale(relin(sum_t a_list[t] (x) b_list[t])) with ONE hybrid key switch whatever the number of terms -> [B][2][L-1][n]"""
+        B, _, L, n = a_list[0].shape
+        T, ap, bp = self._terms(a_list, b_list)
+        out = self.empty((B, 2, L - 1, n)) if out is None else out
+        self._chk(self.lib.hp_dev_ckks_dot_relin_rescale_hks(self.h, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), B, T, ap, bp,
+                                                             self._ptr(key), self._ptr(out)))
+        return out
+
     def poly_from_signed(self, moduli, coeffs):
         """small signed polynomials, coeffs [B][n] (any int64 values, device tensor) -> NTT form [B][L][n]: the words hp_dev_ntt produces
         from the strict residues.  How a ternary secret or an error polynomial gets to the device."""

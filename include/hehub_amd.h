@@ -574,6 +574,40 @@ int hp_dev_ckks_lintrans_bsgs_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, 
 int hp_dev_ckks_mult_relin_rescale_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha,
                                        const uint64_t *moduli_ext, size_t batch, const uint64_t *d_ct1,
                                        const uint64_t *d_ct2, const uint64_t *d_key, uint64_t *d_out);
+/* Lazy relinearisation: sums of ciphertext products that pay ONE hybrid key switch.  Everything after the tensor product is linear in
+ * the quadratic ciphertext (d0, d1, d2), so, residue for residue,
+ *     rescale(relin(sum_t a_t (x) b_t)) = rescale(sum_t (d0_t, d1_t) + switch(sum_t d2_t))
+ * with the noise of one switch and one rounding instead of T: an encrypted dot product, a row of a matrix-matrix product, a sum of
+ * squares, the power-basis combinations of a polynomial evaluation.
+ *
+ * hp_dev_ckks_tensor_sum: d_a and d_b are HOST arrays of `terms` device addresses (an application's ciphertexts are separate objects:
+ * the convention of d_keys in the hoisted calls), each a batch u64[batch][2][L][N] in NTT form.  d_quad u64[batch][3][L][N] =
+ *     d0 = sum_t a0 b0,    d1 = sum_t (a0 b1 + a1 b0),    d2 = sum_t a1 b1        (mod each q_i; every word below 2 q_i)
+ * in the layout of hp_dev_mult_low_level.  The contract is on residues: with one term they are those of hp_dev_mult_low_level, in a
+ * lazy representative of their own.
+ * Every operand word MUST be below 2 * modulus, at either parity level: unlike the other level-B calls this one does not take any
+ * u64 there -- a larger word can wrap the 128-bit sum over the terms unnoticed, and the residues are then undefined.
+ * d_a[t] == d_b[t] (squares) and repeated addresses are allowed; d_quad must not overlap any operand.  One streaming kernel, one
+ * launch per 32 terms, 32 * terms + 24 bytes of device memory traffic per output word; no workspace.
+ * HP_EINVAL before anything is enqueued: L == 0 or L > 32, batch == 0, terms == 0, a NULL array, a NULL or misaligned address in
+ * either array, d_quad NULL, misaligned or overlapping an operand.  HP_EUNSUPPORTED: a modulus of 2^62 or more. */
+int hp_dev_ckks_tensor_sum(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, size_t batch, size_t terms,
+                           const uint64_t *const *d_a, const uint64_t *const *d_b, uint64_t *d_quad);
+/* hp_dev_ckks_relin_rescale_hks: the tail of hp_dev_ckks_mult_relin_rescale_hks on the caller's quadratic ciphertexts d_quad
+ * u64[batch][3][L][N], words below 2q (what hp_dev_mult_low_level and hp_dev_ckks_tensor_sum write): hybrid relinearisation of d2,
+ * + (d0, d1), rescale by q_{L-1} -> d_out u64[batch][2][L-1][N].  The same code as the fused call after its tensor product: on the
+ * same quad, the same words.  The workspace is the fused call's minus its quad block.
+ * HP_EINVAL as for hp_dev_ckks_mult_relin_rescale_hks, and d_out overlapping d_quad. */
+int hp_dev_ckks_relin_rescale_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                  size_t batch, const uint64_t *d_quad, const uint64_t *d_key, uint64_t *d_out);
+/* hp_dev_ckks_dot_relin_rescale_hks: the two calls above in one -- the sum into a workspace quad, then the tail:
+ * d_out u64[batch][2][L-1][N] = rescale(relin(sum_t a_t (x) b_t)), d_a / d_b as for hp_dev_ckks_tensor_sum over the first L moduli
+ * of moduli_ext, with its precondition on the operand words.  d_out must not overlap any operand.  One workspace reservation, a
+ * function of (N, L, k, alpha, batch) alone, never of `terms`.
+ * HP_EINVAL before anything is enqueued: everything either call above refuses. */
+int hp_dev_ckks_dot_relin_rescale_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                      size_t batch, size_t terms, const uint64_t *const *d_a, const uint64_t *const *d_b,
+                                      const uint64_t *d_key, uint64_t *d_out);
 /* Hybrid keys generated on the device.  Sampling stays with the caller: the uniform rows a and the error polynomials e are INPUTS, so
  * a call is deterministic and every output word is pinned by the exact model (tests/test_gpu_hks_keygen.py); what runs here is the
  * arithmetic -- residues of small signed polynomials, batched forward transforms, one streaming multiply-add in Montgomery form.

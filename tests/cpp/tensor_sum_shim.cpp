@@ -1,0 +1,7 @@
+// tensor_sum_shim.cpp -- a C entry point around hpi::tensor_sum_max_terms (hehub_amd/csrc/hp_drop.cpp) so the CPU test-suite can
+// reach the moduli no GPU test uses (tests/test_tensor_sum_host.py).  Test infrastructure only.
+#include "../../hehub_amd/csrc/hp_drop.h"
+
+extern "C" size_t ts_max_terms(const uint64_t *moduli, size_t L, size_t table_max) {
+    return hpi::tensor_sum_max_terms(moduli, L, table_max);
+}
