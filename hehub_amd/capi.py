@@ -145,6 +145,16 @@ SIGNATURES = {
     "hp_dev_ckks_tensor_sum": (INT, [P, szt, szt, P, szt, szt, P, P, P]),
     "hp_dev_ckks_relin_rescale_hks": (INT, [P, szt, szt, szt, szt, P, szt, P, P, P]),
     "hp_dev_ckks_dot_relin_rescale_hks": (INT, [P, szt, szt, szt, szt, P, szt, szt, P, P, P, P]),
+    # a key generated for key_L0 >= L ciphertext moduli: the plain call's arguments with key_L0 after L
+    "hp_dev_hks_switch_at": (INT, [P, szt, szt, szt, szt, szt, P, szt, P, P, P]),
+    "hp_dev_ckks_rotate_hks_at": (INT, [P, szt, szt, szt, szt, szt, P, szt, szt, P, P, P]),
+    "hp_dev_ckks_conjugate_hks_at": (INT, [P, szt, szt, szt, szt, szt, P, szt, P, P, P]),
+    "hp_dev_ckks_rotate_hoisted_hks_at": (INT, [P, szt, szt, szt, szt, szt, P, szt, szt, P, P, P, P, P]),
+    "hp_dev_ckks_lintrans_hks_at": (INT, [P, szt, szt, szt, szt, szt, P, szt, szt, P, P, P, P, P, P]),
+    "hp_dev_ckks_lintrans_bsgs_hks_at": (INT, [P, szt, szt, szt, szt, szt, P, szt, szt, P, P, P, szt, P, P, P, P, P, P]),
+    "hp_dev_ckks_mult_relin_rescale_hks_at": (INT, [P, szt, szt, szt, szt, szt, P, szt, P, P, P, P]),
+    "hp_dev_ckks_relin_rescale_hks_at": (INT, [P, szt, szt, szt, szt, szt, P, szt, P, P, P]),
+    "hp_dev_ckks_dot_relin_rescale_hks_at": (INT, [P, szt, szt, szt, szt, szt, P, szt, szt, P, P, P, P]),
     "hp_dev_poly_from_signed": (INT, [P, szt, szt, P, szt, P, P]),
     "hp_dev_hks_keygen": (INT, [P, szt, szt, szt, szt, P, szt, P, P, P, P, P]),
     "hp_dev_hks_keygen_rot": (INT, [P, szt, szt, szt, szt, P, szt, P, P, P, P, P, P]),

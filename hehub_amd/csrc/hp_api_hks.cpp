@@ -103,18 +103,21 @@ struct HksRotations {
 // A hybrid call in progress: the shape, what the caches hold for it and the parity level, as every stage reads them.  Built in two
 // steps because every entry point has argument checks of its own between them: the constructor checks the limits all calls share
 // (rc), open() fetches the plan and the constants and decides the level, which then holds until the entry point returns.
+// key_L0 >= L: the ciphertext moduli the caller's keys (and diagonals) were generated for; the plain entry points are key_L0 == L.
+// It reaches the inner-product launches as KE = key_L0 + k, the rows of one key digit, and nothing else: the plan, the constants,
+// the workspace, the digit stage and ModDown are those of the level's own chain.
 struct HksCall {
     hp_ctx *ctx;
     const uint64_t *mext;
-    size_t logn, L, k, alpha, n = 0, E = 0, nd = 0;
+    size_t logn, L, key_L0, k, alpha, n = 0, E = 0, KE = 0, nd = 0;
     const Plan *plan = nullptr;
     const HksEntry *he = nullptr;
     std::optional<LevelScope> lvl;
     int rc;
 
-    HksCall(hp_ctx *c, size_t logn_, size_t L_, size_t k_, size_t alpha_, const uint64_t *moduli_ext, size_t batch)
-        : ctx(c), mext(moduli_ext), logn(logn_), L(L_), k(k_), alpha(alpha_), rc(limits(batch)) {
-        if (!rc) n = (size_t)1 << logn, E = L + k, nd = (L + alpha - 1) / alpha;
+    HksCall(hp_ctx *c, size_t logn_, size_t L_, size_t key_L0_, size_t k_, size_t alpha_, const uint64_t *moduli_ext, size_t batch)
+        : ctx(c), mext(moduli_ext), logn(logn_), L(L_), key_L0(key_L0_), k(k_), alpha(alpha_), rc(limits(batch)) {
+        if (!rc) n = (size_t)1 << logn, E = L + k, KE = key_L0 + k, nd = (L + alpha - 1) / alpha;
     }
     HksCall(const HksCall &) = delete;   // (one LevelScope per call)
     int limits(size_t batch) const {
@@ -123,6 +126,10 @@ struct HksCall {
         if (alpha < 1 || alpha > HP_HKS_MAX_ALPHA || (L + alpha - 1) / alpha > HP_HKS_MAX_DIGITS)
             return fail(ctx, HP_EINVAL, "unsupported digit size");
         if (batch == 0) return fail(ctx, HP_EINVAL, "empty batch");
+        if (key_L0 < L) return fail(ctx, HP_EINVAL, "the key has fewer moduli than the ciphertext");
+        // (after L's own limits: with key_L0 == L these two can never be what refuses a call)
+        if (key_L0 > HP_MAX_LIMBS || key_L0 + k > HP_MAX_LIMBS) return fail(ctx, HP_EINVAL, "unsupported number of key moduli");
+        if ((key_L0 + alpha - 1) / alpha > HP_HKS_MAX_DIGITS) return fail(ctx, HP_EINVAL, "unsupported digit size of the key");
         return HP_OK;
     }
     int open() {
@@ -170,7 +177,7 @@ struct HksCall {
         if (e) return e;
         t = tail(P, cv);
         ProfScope ps(ctx, "ks_inner");
-        return chk(ctx, hp_launch_hks_inner(plan->d_limbs, (u32)L, (u32)E, (u32)nd, (u32)alpha, (u32)n, (u32)P, lifted, pt, (u32)pt_pstride, key,
+        return chk(ctx, hp_launch_hks_inner(plan->d_limbs, (u32)L, (u32)E, (u32)KE, (u32)nd, (u32)alpha, (u32)n, (u32)P, lifted, pt, (u32)pt_pstride, key,
                                             t.ks, ctx->stream), "hks_inner");
     }
 
@@ -280,26 +287,32 @@ static int no_overlap(hp_ctx *ctx, const char *call, const void *in, size_t in_b
     return HP_OK;
 }
 
-extern "C" int hp_dev_hks_switch(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t batch,
-                      const uint64_t *pt, const uint64_t *key, uint64_t *out) {
+// Every call that takes a key is written once, as its _at form (a key generated for key_L0 >= L ciphertext moduli; hehub_amd.h has
+// the row map); the plain entry point is the case key_L0 == L of the same code.
+extern "C" int hp_dev_hks_switch_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                    size_t batch, const uint64_t *pt, const uint64_t *key, uint64_t *out) {
     HP_ENTER(ctx);
     HP_REQUIRE(ctx, moduli_ext, pt, key, out);
     HP_ALIGNED(ctx, pt, key, out);
-    HksCall c(ctx, logn, L, k, alpha, moduli_ext, batch);
+    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch);
     if (c.rc || c.open()) return c.rc;
     int rc = ws_reserve(ctx, c.switch_words(batch) * 8);
     if (rc) return rc;
     Carver cv(ctx->ws);
     return c.key_switch(batch, pt, L, key, Addend(), out, cv);
 }
+extern "C" int hp_dev_hks_switch(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t batch,
+                      const uint64_t *pt, const uint64_t *key, uint64_t *out) {
+    return hp_dev_hks_switch_at(ctx, logn, L, L, k, alpha, moduli_ext, batch, pt, key, out);
+}
 
 // ckks rotate / conjugate with a hybrid key: moved = gather(ct); out = key_switch(moved[1]); out[0] += moved[0]
-static int dev_hks_automorphism(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *mext, size_t batch,
+static int dev_hks_automorphism(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *mext, size_t batch,
                                 bool conj, size_t step, const uint64_t *ct, const uint64_t *key, uint64_t *out) {
     HP_ENTER(ctx);
     HP_REQUIRE(ctx, mext, ct, key, out);
     HP_ALIGNED(ctx, ct, key, out);
-    HksCall c(ctx, logn, L, k, alpha, mext, batch);
+    HksCall c(ctx, logn, L, key_L0, k, alpha, mext, batch);
     if (c.rc) return c.rc;
     if (!conj && step >= ((size_t)1 << 17)) return fail(ctx, HP_EINVAL, "rotation step out of range");
     if (c.open()) return c.rc;
@@ -313,11 +326,20 @@ static int dev_hks_automorphism(hp_ctx *ctx, size_t logn, size_t L, size_t k, si
 }
 extern "C" int hp_dev_ckks_rotate_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t batch,
                            size_t step, const uint64_t *ct, const uint64_t *rot_key, uint64_t *out) {
-    return dev_hks_automorphism(ctx, logn, L, k, alpha, moduli_ext, batch, false, step, ct, rot_key, out);
+    return dev_hks_automorphism(ctx, logn, L, L, k, alpha, moduli_ext, batch, false, step, ct, rot_key, out);
+}
+extern "C" int hp_dev_ckks_rotate_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                         size_t batch, size_t step, const uint64_t *ct, const uint64_t *rot_key, uint64_t *out) {
+    return dev_hks_automorphism(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch, false, step, ct, rot_key, out);
 }
 extern "C" int hp_dev_ckks_conjugate_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t batch,
                               const uint64_t *ct, const uint64_t *conj_key, uint64_t *out) {
-    return dev_hks_automorphism(ctx, logn, L, k, alpha, moduli_ext, batch, true, 0, ct, conj_key, out);
+    return dev_hks_automorphism(ctx, logn, L, L, k, alpha, moduli_ext, batch, true, 0, ct, conj_key, out);
+}
+extern "C" int hp_dev_ckks_conjugate_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
+                                            const uint64_t *moduli_ext, size_t batch, const uint64_t *ct, const uint64_t *conj_key,
+                                            uint64_t *out) {
+    return dev_hks_automorphism(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch, true, 0, ct, conj_key, out);
 }
 
 // Hoisted rotations: `rotations` automorphisms of every ciphertext, each with its own key, over ONE digit stage.  The digit rows are
@@ -329,13 +351,13 @@ extern "C" int hp_dev_ckks_conjugate_hks(hp_ctx *ctx, size_t logn, size_t L, siz
 // The rotations are processed HOIST_POLYS / batch at a time (at least one, at most one argument table) against the same digit
 // rows: the working set of a pass is that of an unhoisted rotation of HOIST_POLYS ciphertexts, whatever `rotations` is.
 constexpr size_t HOIST_POLYS = 32;
-extern "C" int hp_dev_ckks_rotate_hoisted_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
-                                              size_t batch, size_t rotations, const size_t *steps, const unsigned char *conj,
-                                              const uint64_t *ct, const uint64_t *const *keys, uint64_t *out) {
+extern "C" int hp_dev_ckks_rotate_hoisted_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
+                                                 const uint64_t *moduli_ext, size_t batch, size_t rotations, const size_t *steps,
+                                                 const unsigned char *conj, const uint64_t *ct, const uint64_t *const *keys, uint64_t *out) {
     HP_ENTER(ctx);
     HP_REQUIRE(ctx, moduli_ext, steps, ct, keys, out);
     HP_ALIGNED(ctx, ct, out);
-    HksCall c(ctx, logn, L, k, alpha, moduli_ext, batch);
+    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch);
     if (c.rc) return c.rc;
     if (rotations == 0) return fail(ctx, HP_EINVAL, "rotate_hoisted: no rotations");
     const HksRotations rot = {rotations, steps, conj, keys};
@@ -374,7 +396,7 @@ extern "C" int hp_dev_ckks_rotate_hoisted_hks(hp_ctx *ctx, size_t logn, size_t L
         }
         {
             ProfScope ps(ctx, "ks_inner");
-            if ((rc = chk(ctx, hp_launch_hks_inner_hoisted(c.plan->d_limbs, (u32)L, (u32)E, (u32)nd, (u32)alpha, (u32)n, (u32)batch, (u32)cnt,
+            if ((rc = chk(ctx, hp_launch_hks_inner_hoisted(c.plan->d_limbs, (u32)L, (u32)E, (u32)c.KE, (u32)nd, (u32)alpha, (u32)n, (u32)batch, (u32)cnt,
                                                            lifted, ct + L * n, (u32)(2 * L), ht, t.ks, ctx->stream), "hks_inner_hoisted")))
                 return rc;
         }
@@ -388,6 +410,11 @@ extern "C" int hp_dev_ckks_rotate_hoisted_hks(hp_ctx *ctx, size_t logn, size_t L
     }
     return HP_OK;
 }
+extern "C" int hp_dev_ckks_rotate_hoisted_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                              size_t batch, size_t rotations, const size_t *steps, const unsigned char *conj,
+                                              const uint64_t *ct, const uint64_t *const *keys, uint64_t *out) {
+    return hp_dev_ckks_rotate_hoisted_hks_at(ctx, logn, L, L, k, alpha, moduli_ext, batch, rotations, steps, conj, ct, keys, out);
+}
 
 // Diagonal linear transform, double hoisted: out = sum_r diag_r * rot_r(ct) with one key per rotation, the weighted sum formed in the
 // extended basis Q P BEFORE ModDown.  Everything after the inner product of a switch is linear in its accumulator, so
@@ -397,13 +424,14 @@ extern "C" int hp_dev_ckks_rotate_hoisted_hks(hp_ctx *ctx, size_t logn, size_t L
 // later ones adding to the reduced words of the earlier), finish -- and so is the workspace, whatever `rotations` is: no [b][r] row
 // set, no yp / rem per rotation, no moved c0 (the kernel folds (P mod q_i) diag_r move_r(c0) into polynomial 0 of the accumulator,
 // which ModDown divides by P exactly: finish runs without an addend).
-extern "C" int hp_dev_ckks_lintrans_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
-                                        size_t batch, size_t rotations, const size_t *steps, const unsigned char *conj, const uint64_t *ct,
-                                        const uint64_t *const *keys, const uint64_t *const *diags, uint64_t *out) {
+extern "C" int hp_dev_ckks_lintrans_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
+                                           const uint64_t *moduli_ext, size_t batch, size_t rotations, const size_t *steps,
+                                           const unsigned char *conj, const uint64_t *ct, const uint64_t *const *keys,
+                                           const uint64_t *const *diags, uint64_t *out) {
     HP_ENTER(ctx);
     HP_REQUIRE(ctx, moduli_ext, steps, ct, keys, diags, out);
     HP_ALIGNED(ctx, ct, out);
-    HksCall c(ctx, logn, L, k, alpha, moduli_ext, batch);
+    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch);
     if (c.rc) return c.rc;
     if (rotations == 0) return fail(ctx, HP_EINVAL, "lintrans: no rotations");
     const HksRotations rot = {rotations, steps, conj, keys};
@@ -425,11 +453,16 @@ extern "C" int hp_dev_ckks_lintrans_hks(hp_ctx *ctx, size_t logn, size_t L, size
         if ((rc = c.fill(ht, rot, nullptr, r0, cnt))) return rc;
         std::copy(diags + r0, diags + r0 + cnt, ht.diag);
         ProfScope ps(ctx, "ks_inner");
-        if ((rc = chk(ctx, hp_launch_hks_inner_lintrans(c.plan->d_limbs, c.he->dev, (u32)E, (u32)n, (u32)batch, (u32)cnt, lifted, ct, ht, r0 != 0,
+        if ((rc = chk(ctx, hp_launch_hks_inner_lintrans(c.plan->d_limbs, c.he->dev, (u32)E, (u32)c.KE, (u32)n, (u32)batch, (u32)cnt, lifted, ct, ht, r0 != 0,
                                                         t.ks, ctx->stream), "hks_inner_lintrans")))
             return rc;
     }
     return c.finish(batch, t, Addend(), out);
+}
+extern "C" int hp_dev_ckks_lintrans_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                        size_t batch, size_t rotations, const size_t *steps, const unsigned char *conj, const uint64_t *ct,
+                                        const uint64_t *const *keys, const uint64_t *const *diags, uint64_t *out) {
+    return hp_dev_ckks_lintrans_hks_at(ctx, logn, L, L, k, alpha, moduli_ext, batch, rotations, steps, conj, ct, keys, diags, out);
 }
 
 // Baby-step giant-step form of the diagonal transform: out = sum_g rot_g( sum_i diag_{g,i} * rot_i(ct) ), babies + giants keys for
@@ -445,15 +478,16 @@ extern "C" int hp_dev_ckks_lintrans_hks(hp_ctx *ctx, size_t logn, size_t L, size
 //   7. finish of acc -> out                                  (batch polynomials)
 // The workspace and the pass plan are hpi::hks_bsgs_plan's (hp_drop.h): a function of the shape alone.  The first digit rows and the
 // baby rows are dead after stage 3; the digit rows of stage 5 take their place.
-extern "C" int hp_dev_ckks_lintrans_bsgs_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
-                                             size_t batch, size_t babies, const size_t *baby_steps, const unsigned char *baby_conj,
-                                             const uint64_t *const *baby_keys, size_t giants, const size_t *giant_steps,
-                                             const unsigned char *giant_conj, const uint64_t *const *giant_keys,
-                                             const uint64_t *const *diags, const uint64_t *ct, uint64_t *out) {
+extern "C" int hp_dev_ckks_lintrans_bsgs_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
+                                                const uint64_t *moduli_ext, size_t batch, size_t babies, const size_t *baby_steps,
+                                                const unsigned char *baby_conj, const uint64_t *const *baby_keys, size_t giants,
+                                                const size_t *giant_steps, const unsigned char *giant_conj,
+                                                const uint64_t *const *giant_keys, const uint64_t *const *diags, const uint64_t *ct,
+                                                uint64_t *out) {
     HP_ENTER(ctx);
     HP_REQUIRE(ctx, moduli_ext, baby_steps, baby_keys, giant_steps, giant_keys, diags, ct, out);
     HP_ALIGNED(ctx, ct, out);
-    HksCall c(ctx, logn, L, k, alpha, moduli_ext, batch);
+    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch);
     if (c.rc) return c.rc;
     if (babies == 0 || giants == 0) return fail(ctx, HP_EINVAL, "lintrans_bsgs: no baby steps or no giant steps");
     const HksRotations baby_rot = {babies, baby_steps, baby_conj, baby_keys}, giant_rot = {giants, giant_steps, giant_conj, giant_keys};
@@ -491,7 +525,7 @@ extern "C" int hp_dev_ckks_lintrans_bsgs_hks(hp_ctx *ctx, size_t logn, size_t L,
         HpLinTable ht;
         if ((rc = c.fill(ht, baby_rot, nullptr, i0, cnt))) return rc;
         ProfScope ps(ctx, "ks_inner");
-        if ((rc = chk(ctx, hp_launch_hks_bsgs_babies(c.plan->d_limbs, c.he->dev, (u32)E, (u32)n, (u32)batch, (u32)cnt, (u32)babies, lifted, ct, ht,
+        if ((rc = chk(ctx, hp_launch_hks_bsgs_babies(c.plan->d_limbs, c.he->dev, (u32)E, (u32)c.KE, (u32)n, (u32)batch, (u32)cnt, (u32)babies, lifted, ct, ht,
                                                      baby + i0 * rows, ctx->stream), "hks_bsgs_babies")))
             return rc;
     }
@@ -510,7 +544,7 @@ extern "C" int hp_dev_ckks_lintrans_bsgs_hks(hp_ctx *ctx, size_t logn, size_t L,
             }
             const bool add = to_acc ? acc_written : i0 != 0;
             ProfScope ps(ctx, "ks_inner");
-            int e = chk(ctx, hp_launch_hks_bsgs_presum(c.plan->d_limbs, (u32)E, (u32)n, (u32)batch, (u32)gcnt, (u32)cnt, baby + i0 * rows,
+            int e = chk(ctx, hp_launch_hks_bsgs_presum(c.plan->d_limbs, (u32)L, (u32)E, (u32)c.KE, (u32)n, (u32)batch, (u32)gcnt, (u32)cnt, baby + i0 * rows,
                                                        babies * rows, pt, to_acc ? rows : GK * rows, add, ctx->stream), "hks_bsgs_presum");
             if (e) return e;
             if (to_acc) acc_written = true;
@@ -531,7 +565,7 @@ extern "C" int hp_dev_ckks_lintrans_bsgs_hks(hp_ctx *ctx, size_t logn, size_t L,
             HpLinTable ht;
             if ((rc = c.fill(ht, giant_rot, keyed.data(), c0, cnt))) return rc;
             ProfScope ps(ctx, "ks_inner");
-            if ((rc = chk(ctx, hp_launch_hks_bsgs_giants(c.plan->d_limbs, c.he->dev, (u32)E, (u32)n, (u32)batch, (u32)cnt, (u32)GK,
+            if ((rc = chk(ctx, hp_launch_hks_bsgs_giants(c.plan->d_limbs, c.he->dev, (u32)E, (u32)c.KE, (u32)n, (u32)batch, (u32)cnt, (u32)GK,
                                                          lifted2 + c0 * nd * E * n, u + c0 * 2 * L * n, ht, acc_written, acc, ctx->stream),
                           "hks_bsgs_giants")))
                 return rc;
@@ -539,6 +573,14 @@ extern "C" int hp_dev_ckks_lintrans_bsgs_hks(hp_ctx *ctx, size_t logn, size_t L,
         }
     }
     return c.finish(batch, {acc, yp, rem}, Addend(), out);                                                      // stage 7
+}
+extern "C" int hp_dev_ckks_lintrans_bsgs_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                             size_t batch, size_t babies, const size_t *baby_steps, const unsigned char *baby_conj,
+                                             const uint64_t *const *baby_keys, size_t giants, const size_t *giant_steps,
+                                             const unsigned char *giant_conj, const uint64_t *const *giant_keys,
+                                             const uint64_t *const *diags, const uint64_t *ct, uint64_t *out) {
+    return hp_dev_ckks_lintrans_bsgs_hks_at(ctx, logn, L, L, k, alpha, moduli_ext, batch, babies, baby_steps, baby_conj, baby_keys, giants,
+                                            giant_steps, giant_conj, giant_keys, diags, ct, out);
 }
 
 // What follows the tensor product of a hybrid multiplication, on an open call: hybrid relinearisation of d2, + (d0, d1), rescale by the
@@ -601,13 +643,13 @@ static int relin_rescale(const HksCall &c, size_t batch, const u64 *quad, const 
 }
 
 // ckks::mult_low_level + relinearisation with a hybrid key + rescale by the last ciphertext modulus
-extern "C" int hp_dev_ckks_mult_relin_rescale_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
-                                       size_t batch, const uint64_t *ct1, const uint64_t *ct2, const uint64_t *key,
-                                       uint64_t *out) {
+extern "C" int hp_dev_ckks_mult_relin_rescale_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
+                                                     const uint64_t *moduli_ext, size_t batch, const uint64_t *ct1, const uint64_t *ct2,
+                                                     const uint64_t *key, uint64_t *out) {
     HP_ENTER(ctx);
     HP_REQUIRE(ctx, moduli_ext, ct1, ct2, key, out);
     HP_ALIGNED(ctx, ct1, ct2, key, out);
-    HksCall c(ctx, logn, L, k, alpha, moduli_ext, batch);
+    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch);
     if (c.rc) return c.rc;
     if (L < 2) return fail(ctx, HP_EINVAL, "Unable to drop the only one prime.");
     if (c.open()) return c.rc;
@@ -623,14 +665,20 @@ extern "C" int hp_dev_ckks_mult_relin_rescale_hks(hp_ctx *ctx, size_t logn, size
     }
     return relin_rescale(c, batch, quad, key, out, cv);
 }
+extern "C" int hp_dev_ckks_mult_relin_rescale_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                       size_t batch, const uint64_t *ct1, const uint64_t *ct2, const uint64_t *key,
+                                       uint64_t *out) {
+    return hp_dev_ckks_mult_relin_rescale_hks_at(ctx, logn, L, L, k, alpha, moduli_ext, batch, ct1, ct2, key, out);
+}
 
 // the tail alone, on the caller's quadratic ciphertexts (hp_dev_mult_low_level's or hp_dev_ckks_tensor_sum's)
-extern "C" int hp_dev_ckks_relin_rescale_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
-                                             size_t batch, const uint64_t *d_quad, const uint64_t *d_key, uint64_t *d_out) {
+extern "C" int hp_dev_ckks_relin_rescale_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
+                                                const uint64_t *moduli_ext, size_t batch, const uint64_t *d_quad, const uint64_t *d_key,
+                                                uint64_t *d_out) {
     HP_ENTER(ctx);
     HP_REQUIRE(ctx, moduli_ext, d_quad, d_key, d_out);
     HP_ALIGNED(ctx, d_quad, d_key, d_out);
-    HksCall c(ctx, logn, L, k, alpha, moduli_ext, batch);
+    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch);
     if (c.rc) return c.rc;
     if (L < 2) return fail(ctx, HP_EINVAL, "Unable to drop the only one prime.");
     int rc = no_overlap(ctx, "relin_rescale", d_quad, batch * 3 * L * c.n * 8, d_out, batch * 2 * (L - 1) * c.n * 8);
@@ -639,6 +687,10 @@ extern "C" int hp_dev_ckks_relin_rescale_hks(hp_ctx *ctx, size_t logn, size_t L,
     if ((rc = ws_reserve(ctx, relin_rescale_words(c, batch) * 8))) return rc;
     Carver cv(ctx->ws);
     return relin_rescale(c, batch, d_quad, d_key, d_out, cv);
+}
+extern "C" int hp_dev_ckks_relin_rescale_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                             size_t batch, const uint64_t *d_quad, const uint64_t *d_key, uint64_t *d_out) {
+    return hp_dev_ckks_relin_rescale_hks_at(ctx, logn, L, L, k, alpha, moduli_ext, batch, d_quad, d_key, d_out);
 }
 
 // ---- sums of products: lazy relinearisation ----------------------------------------------------------------------------------------
@@ -700,13 +752,13 @@ extern "C" int hp_dev_ckks_tensor_sum(hp_ctx *ctx, size_t logn, size_t L, const 
 }
 
 // the composition: the sum into a workspace quad, then the tail.  One reservation, a function of the shape alone, never of `terms`
-extern "C" int hp_dev_ckks_dot_relin_rescale_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
-                                                 size_t batch, size_t terms, const uint64_t *const *d_a, const uint64_t *const *d_b,
-                                                 const uint64_t *d_key, uint64_t *d_out) {
+extern "C" int hp_dev_ckks_dot_relin_rescale_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
+                                                    const uint64_t *moduli_ext, size_t batch, size_t terms, const uint64_t *const *d_a,
+                                                    const uint64_t *const *d_b, const uint64_t *d_key, uint64_t *d_out) {
     HP_ENTER(ctx);
     HP_REQUIRE(ctx, moduli_ext, d_a, d_b, d_key, d_out);
     HP_ALIGNED(ctx, d_key, d_out);
-    HksCall c(ctx, logn, L, k, alpha, moduli_ext, batch);
+    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch);
     if (c.rc) return c.rc;
     if (L < 2) return fail(ctx, HP_EINVAL, "Unable to drop the only one prime.");
     const size_t n = c.n;
@@ -721,6 +773,11 @@ extern "C" int hp_dev_ckks_dot_relin_rescale_hks(hp_ctx *ctx, size_t logn, size_
     u64 *quad = cv.take(batch * 3 * L * n);
     if ((rc = tensor_sum(ctx, c.plan->d_limbs, n, L, batch, pass, ts, quad))) return rc;
     return relin_rescale(c, batch, quad, d_key, d_out, cv);
+}
+extern "C" int hp_dev_ckks_dot_relin_rescale_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                                 size_t batch, size_t terms, const uint64_t *const *d_a, const uint64_t *const *d_b,
+                                                 const uint64_t *d_key, uint64_t *d_out) {
+    return hp_dev_ckks_dot_relin_rescale_hks_at(ctx, logn, L, L, k, alpha, moduli_ext, batch, terms, d_a, d_b, d_key, d_out);
 }
 
 // ---- key generation ----------------------------------------------------------------------------------------------------------------
@@ -759,7 +816,7 @@ extern "C" int hp_dev_poly_from_signed(hp_ctx *ctx, size_t logn, size_t L, const
 static int dev_hks_keygen(hp_ctx *ctx, const char *call, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *mext, size_t keys,
                           const HksRotations *rot, const uint64_t *d_s_to, const uint64_t *d_from, const uint64_t *d_a, const int64_t *d_e,
                           uint64_t *d_keys) {
-    HksCall c(ctx, logn, L, k, alpha, mext, keys);
+    HksCall c(ctx, logn, L, L, k, alpha, mext, keys);
     if (c.rc) return c.rc;
     const size_t n = c.n, E = c.E, nd = c.nd, chunks = keygen_chunks(n);
     int rc;

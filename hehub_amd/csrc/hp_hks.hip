@@ -69,15 +69,19 @@ hipError_t hp_launch_hks_modup(const HpLimb *limbs, const HpHksConsts *hc, u32 a
     });
 }
 
-// out[p][half][m][i] = montgomery_128( sum_d D[p][d][m][i] * key[d][half][m][i] ); PT ciphertexts share each key word
+// out[p][half][m][i] = montgomery_128( sum_d D[p][d][m][i] * key[d][half][m][i] ); PT ciphertexts share each key word.
+// The key may have been generated for a longer chain (the _at entry points): its digits have KE >= E rows, of which row
+// km = m + (m >= L ? KE - E : 0) belongs to modulus m of this level -- the ciphertext moduli first, the special primes last.  m is the
+// workgroup's, so km is one scalar; every internal row (digits, accumulators) stays indexed by m over E.  (hks_key_row: all inner kernels)
+__device__ __forceinline__ u32 hks_key_row(u32 m, u32 L, u32 E, u32 KE) { return m + (m >= L ? KE - E : 0u); }
 template <int PT>
-__global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner(const HpLimb *__restrict__ limbs, u32 L, u32 E, u32 nd, u32 alpha, u32 P,
+__global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner(const HpLimb *__restrict__ limbs, u32 L, u32 E, u32 KE, u32 nd, u32 alpha, u32 P,
                                                           u32 n, u32 chunks, const u64 *__restrict__ lifted,
                                                           const u64 *__restrict__ pt, u32 pt_pstride,
                                                           const u64 *__restrict__ key, u64 *__restrict__ out) {
     const u32 PG = (P + PT - 1) / PT;
     const ElemTile tile(n, chunks);
-    const u32 m = tile.row / PG, p0 = (tile.row % PG) * PT;
+    const u32 m = tile.row / PG, p0 = (tile.row % PG) * PT, km = hks_key_row(m, L, E, KE);
     const u64 q = limbs[m].q, mqinv = limbs[m].mqinv;
     const u32 own = (m < L) ? m / alpha : nd;   // the digit this modulus belongs to (none for the special primes)
     for (const u32 i : tile.pairs()) {
@@ -87,8 +91,8 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner(const HpLimb *__rest
 #pragma unroll
             for (int h = 0; h < 2; h++) { hp_acc_zero(acc[c][h][0]); hp_acc_zero(acc[c][h][1]); }
         for (u32 d = 0; d < nd; d++) {
-            const U2 g0 = *reinterpret_cast<const U2 *>(key + (((size_t)d * 2 + 0) * E + m) * n + i);
-            const U2 g1 = *reinterpret_cast<const U2 *>(key + (((size_t)d * 2 + 1) * E + m) * n + i);
+            const U2 g0 = *reinterpret_cast<const U2 *>(key + (((size_t)d * 2 + 0) * KE + km) * n + i);
+            const U2 g1 = *reinterpret_cast<const U2 *>(key + (((size_t)d * 2 + 1) * KE + km) * n + i);
             const u64 kw[2][2] = {{g0.x, g0.y}, {g1.x, g1.y}};
 #pragma unroll
             for (int c = 0; c < PT; c++) {
@@ -113,11 +117,12 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner(const HpLimb *__rest
     }
 }
 
-hipError_t hp_launch_hks_inner(const HpLimb *limbs, u32 L, u32 E, u32 nd, u32 alpha, u32 n, u32 P, const u64 *lifted, const u64 *pt,
+hipError_t hp_launch_hks_inner(const HpLimb *limbs, u32 L, u32 E, u32 KE, u32 nd, u32 alpha, u32 n, u32 P, const u64 *lifted, const u64 *pt,
                                u32 pt_pstride, const u64 *key, u64 *out, hipStream_t stream) {
+    if (KE < E) return hipErrorInvalidValue;
     // two ciphertexts per thread (four: the column accumulators halve the occupancy, measured -5 %)
     const u32 PT = P >= 2 ? 2 : 1;
-    return elem_launch(PT == 2 ? k_hks_inner<2> : k_hks_inner<1>, ((P + PT - 1) / PT) * E, n, stream, limbs, L, E, nd, alpha, P, n,
+    return elem_launch(PT == 2 ? k_hks_inner<2> : k_hks_inner<1>, ((P + PT - 1) / PT) * E, n, stream, limbs, L, E, KE, nd, alpha, P, n,
                        ElemChunks{}, lifted, pt, pt_pstride, key, out);
 }
 
@@ -133,14 +138,14 @@ hipError_t hp_launch_hks_inner(const HpLimb *limbs, u32 L, u32 E, u32 nd, u32 al
 // The units that do not fill a group of eight are numbered plainly -- their rows get fetched by every XCD (from the Infinity
 // Cache after the first) -- so that no XCD idles.  A speed matter only: any placement computes the same words.
 template <int PT>
-__global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner_hoisted(const HpLimb *__restrict__ limbs, u32 L, u32 E, u32 nd, u32 alpha,
+__global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner_hoisted(const HpLimb *__restrict__ limbs, u32 L, u32 E, u32 KE, u32 nd, u32 alpha,
                                                                   u32 P, u32 R, u32 n, u32 chunks, const u64 *__restrict__ lifted,
                                                                   const u64 *__restrict__ pt, u32 pt_pstride, HpHoistTable tab,
                                                                   u64 *__restrict__ out) {
     const u32 PG = (P + PT - 1) / PT, units = E * PG, W = R * chunks;
     u32 unit, w;
     hp_xcd_unit(blockIdx.x, units, W, unit, w);
-    const u32 m = unit / PG, p0 = (unit % PG) * PT, r = w / chunks;
+    const u32 m = unit / PG, p0 = (unit % PG) * PT, r = w / chunks, km = hks_key_row(m, L, E, KE);
     const ElemTile tile(ElemTile::At{unit, w % chunks}, n);
     const u64 q = limbs[m].q, mqinv = limbs[m].mqinv;
     const u32 own = (m < L) ? m / alpha : nd;   // the digit this modulus belongs to (none for the special primes)
@@ -156,8 +161,8 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner_hoisted(const HpLimb
 #pragma unroll
             for (int h = 0; h < 2; h++) { hp_acc_zero(acc[c][h][0]); hp_acc_zero(acc[c][h][1]); }
         for (u32 d = 0; d < nd; d++) {
-            const U2 g0 = ld_nt(key + (((size_t)d * 2 + 0) * E + m) * n + i);
-            const U2 g1 = ld_nt(key + (((size_t)d * 2 + 1) * E + m) * n + i);
+            const U2 g0 = ld_nt(key + (((size_t)d * 2 + 0) * KE + km) * n + i);
+            const U2 g1 = ld_nt(key + (((size_t)d * 2 + 1) * KE + km) * n + i);
             const u64 kw[2][2] = {{g0.x, g0.y}, {g1.x, g1.y}};
 #pragma unroll
             for (int c = 0; c < PT; c++) {
@@ -190,14 +195,14 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner_hoisted(const HpLimb
     }
 }
 
-hipError_t hp_launch_hks_inner_hoisted(const HpLimb *limbs, u32 L, u32 E, u32 nd, u32 alpha, u32 n, u32 P, u32 R, const u64 *lifted,
+hipError_t hp_launch_hks_inner_hoisted(const HpLimb *limbs, u32 L, u32 E, u32 KE, u32 nd, u32 alpha, u32 n, u32 P, u32 R, const u64 *lifted,
                                        const u64 *pt, u32 pt_pstride, const HpHoistTable &tab, u64 *out, hipStream_t stream) {
     if (P == 0 || R == 0) return hipSuccess;
-    if (R > HP_HOIST_TABLE_MAX) return hipErrorInvalidValue;
+    if (R > HP_HOIST_TABLE_MAX || KE < E) return hipErrorInvalidValue;
     // two ciphertexts per thread share the key words and the map's pair, as in k_hks_inner
     const u32 PT = P >= 2 ? 2 : 1, chunks = (n + ELEM_CHUNK - 1) / ELEM_CHUNK;
     const auto k = PT == 2 ? k_hks_inner_hoisted<2> : k_hks_inner_hoisted<1>;
-    k<<<dim3(((P + PT - 1) / PT) * E * R * chunks, 1, 1), ELEM_THREADS, 0, stream>>>(limbs, L, E, nd, alpha, P, R, n, chunks, lifted, pt,
+    k<<<dim3(((P + PT - 1) / PT) * E * R * chunks, 1, 1), ELEM_THREADS, 0, stream>>>(limbs, L, E, KE, nd, alpha, P, R, n, chunks, lifted, pt,
                                                                                  pt_pstride, tab, out);
     return hipGetLastError();
 }
@@ -241,14 +246,14 @@ hipError_t hp_launch_hks_inner_hoisted(const HpLimb *limbs, u32 L, u32 E, u32 nd
 enum { HKS_LT_FLAT = 0, HKS_LT_GIANT = 1, HKS_LT_BABY = 2 };
 template <int FLAV>
 __global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner_lintrans(const HpLimb *__restrict__ limbs, const HpHksConsts *__restrict__ hc,
-                                                                   u32 P, u32 R, u32 Rtot, u32 n, u32 chunks,
+                                                                   u32 KE, u32 P, u32 R, u32 Rtot, u32 n, u32 chunks,
                                                                    const u64 *__restrict__ lifted, const u64 *__restrict__ ct,
                                                                    HpLinTable tab, u32 add_prev, u64 *__restrict__ out) {
     const u32 L = hc->L, E = hc->E, nd = hc->nd, alpha = hc->alpha;
     const u32 units = E * P, W = FLAV == HKS_LT_BABY ? R * chunks : chunks;
     u32 unit, w;
     HP_XCD_UNIT(blockIdx.x, units, W, unit, w)   // (hp_device.h: why not the function here)
-    const u32 m = unit / P, p = unit % P;
+    const u32 m = unit / P, p = unit % P, km = hks_key_row(m, L, E, KE);   // (keys and diagonals: rows of the chain they were made for)
     const ElemTile tile(ElemTile::At{unit, w % chunks}, n, HKS_LT_CHUNK);
     const u32 r_first = FLAV == HKS_LT_BABY ? w / chunks : 0, r_end = FLAV == HKS_LT_BABY ? r_first + 1 : R;
     const u64 q = limbs[m].q, mqinv = limbs[m].mqinv, two_q = limbs[m].two_q, r64 = limbs[m].r64, r64h = limbs[m].r64h;
@@ -288,15 +293,15 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner_lintrans(const HpLim
                 return U2{v.y, v.x};
             };
             U2 dw{1, 1};
-            if (dg) dw = *reinterpret_cast<const U2 *>(dg + (size_t)m * n + i);
+            if (dg) dw = *reinterpret_cast<const U2 *>(dg + (size_t)km * n + i);
             U2 c0{0, 0};
             if (fold) c0 = moved(c0row);
             HpAcc acc[2][2];   // carry-save columns (hp_device.h)
 #pragma unroll
             for (int h = 0; h < 2; h++) { hp_acc_zero(acc[h][0]); hp_acc_zero(acc[h][1]); }
             for (u32 d = 0; d < nd; d++) {
-                const U2 g0 = ld_nt(key + (((size_t)d * 2 + 0) * E + m) * n + i);
-                const U2 g1 = ld_nt(key + (((size_t)d * 2 + 1) * E + m) * n + i);
+                const U2 g0 = ld_nt(key + (((size_t)d * 2 + 0) * KE + km) * n + i);
+                const U2 g1 = ld_nt(key + (((size_t)d * 2 + 1) * KE + km) * n + i);
                 const u64 kw[2][2] = {{g0.x, g0.y}, {g1.x, g1.y}};
                 const U2 t = moved((d == own) ? c1row : lifted + ((pr * nd + d) * E + m) * n);
 #pragma unroll
@@ -331,26 +336,26 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner_lintrans(const HpLim
 }
 
 template <int FLAV>
-static hipError_t hks_lintrans_launch(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 n, u32 P, u32 R, u32 Rtot, const u64 *lifted,
-                                      const u64 *ct, const HpLinTable &tab, bool add_prev, u64 *out, hipStream_t stream) {
+static hipError_t hks_lintrans_launch(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 KE, u32 n, u32 P, u32 R, u32 Rtot,
+                                      const u64 *lifted, const u64 *ct, const HpLinTable &tab, bool add_prev, u64 *out, hipStream_t stream) {
     if (P == 0 || R == 0) return hipSuccess;
-    if (R > HP_HOIST_TABLE_MAX) return hipErrorInvalidValue;
+    if (R > HP_HOIST_TABLE_MAX || KE < E) return hipErrorInvalidValue;
     const u32 chunks = (n + HKS_LT_CHUNK - 1) / HKS_LT_CHUNK, W = FLAV == HKS_LT_BABY ? R * chunks : chunks;
-    k_hks_inner_lintrans<FLAV><<<dim3(P * E * W, 1, 1), ELEM_THREADS, 0, stream>>>(limbs, hc, P, R, Rtot, n, chunks, lifted, ct, tab,
+    k_hks_inner_lintrans<FLAV><<<dim3(P * E * W, 1, 1), ELEM_THREADS, 0, stream>>>(limbs, hc, KE, P, R, Rtot, n, chunks, lifted, ct, tab,
                                                                                  add_prev ? 1u : 0u, out);
     return hipGetLastError();
 }
-hipError_t hp_launch_hks_inner_lintrans(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 n, u32 P, u32 R, const u64 *lifted,
+hipError_t hp_launch_hks_inner_lintrans(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 KE, u32 n, u32 P, u32 R, const u64 *lifted,
                                         const u64 *ct, const HpLinTable &tab, bool add_prev, u64 *acc, hipStream_t stream) {
-    return hks_lintrans_launch<HKS_LT_FLAT>(limbs, hc, E, n, P, R, R, lifted, ct, tab, add_prev, acc, stream);
+    return hks_lintrans_launch<HKS_LT_FLAT>(limbs, hc, E, KE, n, P, R, R, lifted, ct, tab, add_prev, acc, stream);
 }
-hipError_t hp_launch_hks_bsgs_babies(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 n, u32 P, u32 R, u32 Rtot, const u64 *lifted,
-                                     const u64 *ct, const HpLinTable &tab, u64 *baby, hipStream_t stream) {
-    return hks_lintrans_launch<HKS_LT_BABY>(limbs, hc, E, n, P, R, Rtot, lifted, ct, tab, false, baby, stream);
+hipError_t hp_launch_hks_bsgs_babies(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 KE, u32 n, u32 P, u32 R, u32 Rtot,
+                                     const u64 *lifted, const u64 *ct, const HpLinTable &tab, u64 *baby, hipStream_t stream) {
+    return hks_lintrans_launch<HKS_LT_BABY>(limbs, hc, E, KE, n, P, R, Rtot, lifted, ct, tab, false, baby, stream);
 }
-hipError_t hp_launch_hks_bsgs_giants(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 n, u32 P, u32 R, u32 Rtot, const u64 *lifted,
-                                     const u64 *u, const HpLinTable &tab, bool add_prev, u64 *acc, hipStream_t stream) {
-    return hks_lintrans_launch<HKS_LT_GIANT>(limbs, hc, E, n, P, R, Rtot, lifted, u, tab, add_prev, acc, stream);
+hipError_t hp_launch_hks_bsgs_giants(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 KE, u32 n, u32 P, u32 R, u32 Rtot,
+                                     const u64 *lifted, const u64 *u, const HpLinTable &tab, bool add_prev, u64 *acc, hipStream_t stream) {
+    return hks_lintrans_launch<HKS_LT_GIANT>(limbs, hc, E, KE, n, P, R, Rtot, lifted, u, tab, add_prev, acc, stream);
 }
 
 // Pre-sum of the baby-step giant-step transform: pre_g = sum_i diag_{g,i} * baby_i in the extended basis, the outer sum of the flat
@@ -365,12 +370,13 @@ hipError_t hp_launch_hks_bsgs_giants(const HpLimb *limbs, const HpHksConsts *hc,
 // `chunks` workgroups apart.  Unmeasured.
 #define HKS_PRE_GT 4
 template <int GT>
-__global__ void __launch_bounds__(ELEM_THREADS) k_hks_bsgs_presum(const HpLimb *__restrict__ limbs, u32 E, u32 G, u32 Bn, u32 n, u32 chunks,
+__global__ void __launch_bounds__(ELEM_THREADS) k_hks_bsgs_presum(const HpLimb *__restrict__ limbs, u32 L, u32 E, u32 KE, u32 G, u32 Bn, u32 n, u32 chunks,
                                                                 const u64 *__restrict__ baby, size_t baby_pstride, HpPreTable tab,
                                                                 size_t dst_pstride, u32 add_prev) {
     const u32 tiles = (G + GT - 1) / GT;
     const ElemTile tile(n, chunks, HKS_LT_CHUNK);
     const u32 g0 = (tile.row % tiles) * GT, m = (tile.row / tiles) % E, b = tile.row / (tiles * E);
+    const u32 km = hks_key_row(m, L, E, KE);   // the diagonal's row of modulus m (a diagonal has KE rows)
     const u64 q = limbs[m].q, mqinv = limbs[m].mqinv, two_q = limbs[m].two_q, r64 = limbs[m].r64, r64h = limbs[m].r64h;
     const u64 *__restrict__ brow = baby + (size_t)b * baby_pstride + (size_t)m * n;   // baby i, half h: + (i * 2 + h) * E * n
     for (const u32 i : tile.pairs()) {
@@ -386,7 +392,7 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_bsgs_presum(const HpLimb *
             for (int c = 0; c < GT; c++) {
                 const u64 *__restrict__ dg = g0 + c < G ? tab.diag[(g0 + c) * Bn + j] : nullptr;
                 if (dg) {
-                    const U2 dw = ld_nt(dg + (size_t)m * n + i);
+                    const U2 dw = ld_nt(dg + (size_t)km * n + i);
                     hp_mac2(sum[c][0][0], v0.x, dw.x, sum[c][0][1], v0.y, dw.y);
                     hp_mac2(sum[c][1][0], v1.x, dw.x, sum[c][1][1], v1.y, dw.y);
                 }
@@ -413,12 +419,12 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_bsgs_presum(const HpLimb *
     }
 }
 
-hipError_t hp_launch_hks_bsgs_presum(const HpLimb *limbs, u32 E, u32 n, u32 P, u32 giants, u32 babies, const u64 *baby, size_t baby_pstride,
-                                     const HpPreTable &tab, size_t dst_pstride, bool add_prev, hipStream_t stream) {
+hipError_t hp_launch_hks_bsgs_presum(const HpLimb *limbs, u32 L, u32 E, u32 KE, u32 n, u32 P, u32 giants, u32 babies, const u64 *baby,
+                                     size_t baby_pstride, const HpPreTable &tab, size_t dst_pstride, bool add_prev, hipStream_t stream) {
     if (P == 0 || giants == 0 || babies == 0) return hipSuccess;
-    if (giants > HP_BSGS_GIANT_MAX || giants * babies > HP_BSGS_DIAG_MAX) return hipErrorInvalidValue;
+    if (giants > HP_BSGS_GIANT_MAX || giants * babies > HP_BSGS_DIAG_MAX || KE < E || L > E) return hipErrorInvalidValue;
     const u32 tiles = (giants + HKS_PRE_GT - 1) / HKS_PRE_GT;
-    return elem_launch_cw(k_hks_bsgs_presum<HKS_PRE_GT>, HKS_LT_CHUNK, P * E * tiles, n, stream, limbs, E, giants, babies, n, ElemChunks{},
+    return elem_launch_cw(k_hks_bsgs_presum<HKS_PRE_GT>, HKS_LT_CHUNK, P * E * tiles, n, stream, limbs, L, E, KE, giants, babies, n, ElemChunks{},
                           baby, baby_pstride, tab, dst_pstride, add_prev ? 1u : 0u);
 }
 

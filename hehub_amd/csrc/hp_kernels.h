@@ -233,7 +233,10 @@ hipError_t hp_launch_hks_moddown(const HpLimb *limbs, const HpHksConsts *hc, u32
                                  hipStream_t stream);
 hipError_t hp_launch_hks_modup(const HpLimb *limbs, const HpHksConsts *hc, u32 alpha, u32 nd, u32 n, u32 P, const u64 *coef,
                                u64 *lifted, hipStream_t stream);
-hipError_t hp_launch_hks_inner(const HpLimb *limbs, u32 L, u32 E, u32 nd, u32 alpha, u32 n, u32 P, const u64 *lifted, const u64 *pt,
+// The inner products.  KE >= E: the rows of one digit of every key (and of every diagonal) they read -- E for a key of this chain;
+// key_L0 + k for one generated for key_L0 >= L ciphertext moduli (the _at entry points), of which modulus m of the level is row
+// m + (m >= L ? KE - E : 0): the ciphertext moduli first, the special primes last.  Digit rows, baby rows and accumulators have E rows.
+hipError_t hp_launch_hks_inner(const HpLimb *limbs, u32 L, u32 E, u32 KE, u32 nd, u32 alpha, u32 n, u32 P, const u64 *lifted, const u64 *pt,
                                u32 pt_pstride, const u64 *key, u64 *out, hipStream_t stream);
 // hoisted rotations: the inner product of R rotations over ONE set of digit rows (of the unrotated polynomials), rotation r reading
 // them through map[r] (a cycle map of the context's cache; NULL: the involution) and multiplying by key[r]
@@ -243,7 +246,7 @@ struct HpHoistTable {
     const u64 *key[HP_HOIST_TABLE_MAX];
     const u32 *map[HP_HOIST_TABLE_MAX];
 };
-hipError_t hp_launch_hks_inner_hoisted(const HpLimb *limbs, u32 L, u32 E, u32 nd, u32 alpha, u32 n, u32 P, u32 R, const u64 *lifted,
+hipError_t hp_launch_hks_inner_hoisted(const HpLimb *limbs, u32 L, u32 E, u32 KE, u32 nd, u32 alpha, u32 n, u32 P, u32 R, const u64 *lifted,
                                        const u64 *pt, u32 pt_pstride, const HpHoistTable &tab, u64 *out, hipStream_t stream);
 // diagonal linear transform in the extended basis (hp_dev_ckks_lintrans_hks): the R rotations of the table weighted and summed
 // inside the thread, ct [P][2][L][n] (digit rows `lifted` of its polynomials 1, as for the hoisted product)
@@ -253,9 +256,9 @@ hipError_t hp_launch_hks_inner_hoisted(const HpLimb *limbs, u32 L, u32 E, u32 nd
 struct HpLinTable {   // a table of its own: the hoisted kernel's argument block stays as it is
     const u64 *key[HP_HOIST_TABLE_MAX];
     const u32 *map[HP_HOIST_TABLE_MAX];
-    const u64 *diag[HP_HOIST_TABLE_MAX];   // [E][n] plain words below 2 * modulus, NTT form; NULL: the constant 1
+    const u64 *diag[HP_HOIST_TABLE_MAX];   // [KE][n] plain words below 2 * modulus, NTT form; NULL: the constant 1
 };
-hipError_t hp_launch_hks_inner_lintrans(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 n, u32 P, u32 R, const u64 *lifted,
+hipError_t hp_launch_hks_inner_lintrans(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 KE, u32 n, u32 P, u32 R, const u64 *lifted,
                                         const u64 *ct, const HpLinTable &tab, bool add_prev, u64 *acc, hipStream_t stream);
 // Baby-step giant-step transform (hp_dev_ckks_lintrans_bsgs_hks): two more flavours of the accumulate kernel, and the pre-sum.
 //   babies: rotation r of the table -> its own row set, nothing summed: baby [P][Rtot][2][E][n] (the launch writes the R sets from
@@ -264,20 +267,20 @@ hipError_t hp_launch_hks_inner_lintrans(const HpLimb *limbs, const HpHksConsts *
 //   giants: the flat call's sum with every rotation reading ITS OWN polynomial -- digit rows `lifted` and rows u of polynomial
 //           p * Rtot + r, u [P][Rtot][2][L][n] -- and no diagonal -> acc [P][2][E][n], words below 2 * modulus, add_prev as above
 static_assert(HP_BSGS_TABLE_MAX == HP_HOIST_TABLE_MAX, "the plan of hp_drop.h counts in argument tables");
-hipError_t hp_launch_hks_bsgs_babies(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 n, u32 P, u32 R, u32 Rtot, const u64 *lifted,
-                                     const u64 *ct, const HpLinTable &tab, u64 *baby, hipStream_t stream);
-hipError_t hp_launch_hks_bsgs_giants(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 n, u32 P, u32 R, u32 Rtot, const u64 *lifted,
-                                     const u64 *u, const HpLinTable &tab, bool add_prev, u64 *acc, hipStream_t stream);
+hipError_t hp_launch_hks_bsgs_babies(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 KE, u32 n, u32 P, u32 R, u32 Rtot,
+                                     const u64 *lifted, const u64 *ct, const HpLinTable &tab, u64 *baby, hipStream_t stream);
+hipError_t hp_launch_hks_bsgs_giants(const HpLimb *limbs, const HpHksConsts *hc, u32 E, u32 KE, u32 n, u32 P, u32 R, u32 Rtot,
+                                     const u64 *lifted, const u64 *u, const HpLinTable &tab, bool add_prev, u64 *acc, hipStream_t stream);
 // pre-sum: dst[g][b][h][m] = sum_i diag[g * babies + i][m] * baby[b][i][h][m] for the `giants` giants and `babies` babies of the
 // table (baby row set i of ciphertext b at baby + b * baby_pstride + i * 2 E n; giant g's rows of ciphertext b at
 // dst[g] + b * dst_pstride), words below 2 * modulus; a NULL diagonal: the term is absent; add_prev: added to what dst holds.
 // babies <= hpi::hks_bsgs_plan's baby_pass (the 128-bit sums), giants * babies <= HP_BSGS_DIAG_MAX, giants <= HP_BSGS_GIANT_MAX
 struct HpPreTable {
-    const u64 *diag[HP_BSGS_DIAG_MAX];   // [E][n] plain words below 2 * modulus, NTT form
+    const u64 *diag[HP_BSGS_DIAG_MAX];   // [KE][n] plain words below 2 * modulus, NTT form
     u64 *dst[HP_BSGS_GIANT_MAX];
 };
-hipError_t hp_launch_hks_bsgs_presum(const HpLimb *limbs, u32 E, u32 n, u32 P, u32 giants, u32 babies, const u64 *baby, size_t baby_pstride,
-                                     const HpPreTable &tab, size_t dst_pstride, bool add_prev, hipStream_t stream);
+hipError_t hp_launch_hks_bsgs_presum(const HpLimb *limbs, u32 L, u32 E, u32 KE, u32 n, u32 P, u32 giants, u32 babies, const u64 *baby,
+                                     size_t baby_pstride, const HpPreTable &tab, size_t dst_pstride, bool add_prev, hipStream_t stream);
 // key generation (hp_dev_hks_keygen / _rot): keys [R][nd][2][E][n] with NTT(e[r][d]) in keys[r][d][0] on entry (any u64 words) ->
 //   keys[r][d][0][m] = (NTT(e) - a[r][d][m] * s_to[m] + (m in digit d) * (P mod q_m) * from_r[m]) * 2^64,  keys[r][d][1][m] = a * 2^64,
 // canonical residues.  a [R][nd][E][n], or NULL: the rows already in keys[r][d][1].  from_r = s_from [R][E][n] (maps == NULL), or

@@ -425,29 +425,38 @@ class Engine:
                                                         self._ptr(x), self._ptr(out)))
         return out
 
-    def hks_switch(self, moduli_ext, k: int, alpha: int, pt, key):
-        """hybrid key switch (extension): pt [B][L][n] NTT form, key [dnum][2][L+k][n] -> [B][2][L][n]."""
+    def _hks(self, name, key_L0, logn, L, *rest):
+        """a hybrid call over keys: the plain entry point, or with key_L0 (the ciphertext moduli the keys -- and diagonals -- were
+        generated for, >= L: one top-level key set serves every level) its _at form, which takes key_L0 after L"""
+        if key_L0 is None:
+            return self._chk(getattr(self.lib, name)(self.h, logn, L, *rest))
+        return self._chk(getattr(self.lib, name + "_at")(self.h, logn, L, int(key_L0), *rest))
+
+    def hks_switch(self, moduli_ext, k: int, alpha: int, pt, key, key_L0=None):
+        """hybrid key switch (extension): pt [B][L][n] NTT form, key [dnum][2][L+k][n] -> [B][2][L][n].  key_L0 (here and in every
+        hybrid method over keys): the keys are [ceil(key_L0/alpha)][2][key_L0+k][n], generated for key_L0 >= L moduli; moduli_ext stays
+        the level's chain."""
         B, L, n = pt.shape
         out = self.empty((B, 2, L, n))
-        self._chk(self.lib.hp_dev_hks_switch(self.h, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), B, self._ptr(pt),
-                                             self._ptr(key), self._ptr(out)))
+        self._hks("hp_dev_hks_switch", key_L0, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), B, self._ptr(pt),
+                  self._ptr(key), self._ptr(out))
         return out
 
-    def ckks_rotate_hks(self, moduli_ext, k: int, alpha: int, ct, key, step: int):
+    def ckks_rotate_hks(self, moduli_ext, k: int, alpha: int, ct, key, step: int, key_L0=None):
         B, _, L, n = ct.shape
         out = self.empty((B, 2, L, n))
-        self._chk(self.lib.hp_dev_ckks_rotate_hks(self.h, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), B, step,
-                                                  self._ptr(ct), self._ptr(key), self._ptr(out)))
+        self._hks("hp_dev_ckks_rotate_hks", key_L0, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), B, step,
+                  self._ptr(ct), self._ptr(key), self._ptr(out))
         return out
 
-    def ckks_conjugate_hks(self, moduli_ext, k: int, alpha: int, ct, key):
+    def ckks_conjugate_hks(self, moduli_ext, k: int, alpha: int, ct, key, key_L0=None):
         B, _, L, n = ct.shape
         out = self.empty((B, 2, L, n))
-        self._chk(self.lib.hp_dev_ckks_conjugate_hks(self.h, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), B,
-                                                     self._ptr(ct), self._ptr(key), self._ptr(out)))
+        self._hks("hp_dev_ckks_conjugate_hks", key_L0, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), B,
+                  self._ptr(ct), self._ptr(key), self._ptr(out))
         return out
 
-    def ckks_rotate_hoisted_hks(self, moduli_ext, k: int, alpha: int, ct, keys, steps, conj=None):
+    def ckks_rotate_hoisted_hks(self, moduli_ext, k: int, alpha: int, ct, keys, steps, conj=None, key_L0=None):
         """every ciphertext of ct [B][2][L][n] rotated by steps[r] (conjugated where conj[r]) under ITS hybrid key keys[r] (device
         tensors), all rotations sharing one digit decomposition of c1 -> [B][R][2][L][n]."""
         B, _, L, n = ct.shape
@@ -457,13 +466,14 @@ class Engine:
         kp = (capi.P * R)(*[key.data_ptr() for key in keys])
         st = (C.c_size_t * R)(*[int(s) for s in steps])
         cj = (C.c_ubyte * R)(*[1 if c else 0 for c in conj]) if conj is not None else None
-        self._chk(self.lib.hp_dev_ckks_rotate_hoisted_hks(self.h, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), B, R, st, cj,
-                                                          self._ptr(ct), kp, self._ptr(out)))
+        self._hks("hp_dev_ckks_rotate_hoisted_hks", key_L0, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), B, R, st, cj,
+                  self._ptr(ct), kp, self._ptr(out))
         return out
 
-    def ckks_lintrans_hks(self, moduli_ext, k: int, alpha: int, ct, keys, steps, diags, conj=None):
+    def ckks_lintrans_hks(self, moduli_ext, k: int, alpha: int, ct, keys, steps, diags, conj=None, key_L0=None):
         """sum_r diags[r] * rot_r(ct) for ct [B][2][L][n] with one hybrid key per rotation, the weighted sum formed before ONE ModDown
-        -> [B][2][L][n].  diags[r]: device tensor [L+k][n], NTT form over the extended chain, plain lazy words; None: the constant 1."""
+        -> [B][2][L][n].  diags[r]: device tensor [L+k][n], NTT form over the extended chain, plain lazy words; None: the constant 1.
+        With key_L0 the diagonals are [key_L0+k][n] like the keys' digits: encoded once over the top chain."""
         B, _, L, n = ct.shape
         R = len(keys)
         assert len(steps) == R and len(diags) == R and (conj is None or len(conj) == R)
@@ -472,16 +482,17 @@ class Engine:
         dp = (capi.P * R)(*[None if d is None else d.data_ptr() for d in diags])
         st = (C.c_size_t * R)(*[int(s) for s in steps])
         cj = (C.c_ubyte * R)(*[1 if c else 0 for c in conj]) if conj is not None else None
-        self._chk(self.lib.hp_dev_ckks_lintrans_hks(self.h, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), B, R, st, cj,
-                                                    self._ptr(ct), kp, dp, self._ptr(out)))
+        self._hks("hp_dev_ckks_lintrans_hks", key_L0, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), B, R, st, cj,
+                  self._ptr(ct), kp, dp, self._ptr(out))
         return out
 
     def ckks_lintrans_bsgs_hks(self, moduli_ext, k: int, alpha: int, ct, baby_keys, baby_steps, giant_keys, giant_steps, diags,
-                               baby_conj=None, giant_conj=None):
+                               baby_conj=None, giant_conj=None, key_L0=None):
         """sum_g rot_g( sum_i diags[g][i] * rot_i(ct) ) for ct [B][2][L][n]: len(baby_keys) + len(giant_keys) hybrid keys for their
         product of diagonals -> [B][2][L][n].  diags[g][i]: device tensor [L+k][n], NTT form over the extended chain, plain lazy words,
         NOT rotated by the call (pass rot_g^-1 of the matrix's diagonal g + i); None: the term is ABSENT (in ckks_lintrans_hks None is
-        the constant 1).  A key may be None where the step is 0 and the entry no conjugation: the identity, no key switch."""
+        the constant 1).  A key may be None where the step is 0 and the entry no conjugation: the identity, no key switch.
+        With key_L0 the diagonals are [key_L0+k][n] like the keys' digits."""
         B, _, L, n = ct.shape
         nb, ng = len(baby_keys), len(giant_keys)
         assert len(baby_steps) == nb and len(giant_steps) == ng and len(diags) == ng and all(len(row) == nb for row in diags)
@@ -497,15 +508,15 @@ class Engine:
         bs, bc, bk = table(baby_keys, baby_steps, baby_conj)
         gs, gc, gk = table(giant_keys, giant_steps, giant_conj)
         dp = (capi.P * (ng * nb))(*[None if d is None else d.data_ptr() for row in diags for d in row])
-        self._chk(self.lib.hp_dev_ckks_lintrans_bsgs_hks(self.h, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), B, nb, bs, bc, bk,
-                                                         ng, gs, gc, gk, dp, self._ptr(ct), self._ptr(out)))
+        self._hks("hp_dev_ckks_lintrans_bsgs_hks", key_L0, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), B, nb, bs, bc, bk,
+                  ng, gs, gc, gk, dp, self._ptr(ct), self._ptr(out))
         return out
 
-    def ckks_mult_hks(self, moduli_ext, k: int, alpha: int, ct1, ct2, key, out=None):
+    def ckks_mult_hks(self, moduli_ext, k: int, alpha: int, ct1, ct2, key, out=None, key_L0=None):
         B, _, L, n = ct1.shape
         out = self.empty((B, 2, L - 1, n)) if out is None else out
-        self._chk(self.lib.hp_dev_ckks_mult_relin_rescale_hks(self.h, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), B,
-                                                              self._ptr(ct1), self._ptr(ct2), self._ptr(key), self._ptr(out)))
+        self._hks("hp_dev_ckks_mult_relin_rescale_hks", key_L0, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), B,
+                  self._ptr(ct1), self._ptr(ct2), self._ptr(key), self._ptr(out))
         return out
 
     @staticmethod
@@ -526,21 +537,21 @@ class Engine:
         self._chk(self.lib.hp_dev_ckks_tensor_sum(self.h, n.bit_length() - 1, L, _u64arr(moduli), B, T, ap, bp, self._ptr(out)))
         return out
 
-    def ckks_relin_rescale_hks(self, moduli_ext, k: int, alpha: int, quad, key, out=None):
+    def ckks_relin_rescale_hks(self, moduli_ext, k: int, alpha: int, quad, key, out=None, key_L0=None):
         """quad [B][3][L][n] (mult_low_level's or ckks_tensor_sum's) -> hybrid relinearisation + rescale, [B][2][L-1][n]"""
         B, _, L, n = quad.shape
         out = self.empty((B, 2, L - 1, n)) if out is None else out
-        self._chk(self.lib.hp_dev_ckks_relin_rescale_hks(self.h, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), B,
-                                                         self._ptr(quad), self._ptr(key), self._ptr(out)))
+        self._hks("hp_dev_ckks_relin_rescale_hks", key_L0, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), B,
+                  self._ptr(quad), self._ptr(key), self._ptr(out))
         return out
 
-    def ckks_dot_hks(self, moduli_ext, k: int, alpha: int, a_list, b_list, key, out=None):
+    def ckks_dot_hks(self, moduli_ext, k: int, alpha: int, a_list, b_list, key, out=None, key_L0=None):
         """rescale(relin(sum_t a_list[t] (x) b_list[t])) with ONE hybrid key switch whatever the number of terms -> [B][2][L-1][n]"""
         B, _, L, n = a_list[0].shape
         T, ap, bp = self._terms(a_list, b_list)
         out = self.empty((B, 2, L - 1, n)) if out is None else out
-        self._chk(self.lib.hp_dev_ckks_dot_relin_rescale_hks(self.h, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), B, T, ap, bp,
-                                                             self._ptr(key), self._ptr(out)))
+        self._hks("hp_dev_ckks_dot_relin_rescale_hks", key_L0, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), B, T, ap, bp,
+                  self._ptr(key), self._ptr(out))
         return out
 
     def poly_from_signed(self, moduli, coeffs):

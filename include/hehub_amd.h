@@ -608,6 +608,47 @@ int hp_dev_ckks_relin_rescale_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, 
 int hp_dev_ckks_dot_relin_rescale_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
                                       size_t batch, size_t terms, const uint64_t *const *d_a, const uint64_t *const *d_b,
                                       const uint64_t *d_key, uint64_t *d_out);
+/* Hybrid keys generated for key_L0 ciphertext moduli used at a LOWER level L <= key_L0 -- extension (1) for the hybrid path: one
+ * top-level key set serves every level of a circuit (hp_dev_ckks_mult_relin_rescale_hks returns L-1 limbs; the next call takes the
+ * same keys).  Every _at call has the plain call's arguments with key_L0 after L:
+ *   - moduli_ext stays the chain of the LEVEL: q_0..q_{L-1}, p_0..p_{k-1};
+ *   - every key is u64[ceil(key_L0/alpha)][2][key_L0+k][N], as hp_dev_hks_keygen writes it for q_0..q_{key_L0-1}, p_0..p_{k-1};
+ *     digit rows d >= ceil(L/alpha) and modulus rows L..key_L0-1 are ignored, the special primes are the last k rows;
+ *   - the diagonals of the two linear transforms follow the same rule: u64[key_L0+k][N], encoded once over the top chain, read in
+ *     rows 0..L-1 and key_L0..key_L0+k-1;
+ *   - ciphertexts, outputs and workspace are those of the plain call at L.
+ * Digits are cut at multiples of alpha from limb 0, so the limbs below L of level digit d are a subset of top digit d, and row d of
+ * the top key restricted to those moduli IS the key hp_dev_hks_keygen writes for the level's chain from the same a rows and the same
+ * e (P >= every digit product holds a fortiori).  Identical, word for word and at either parity level, to the plain entry point on
+ * the extracted sub-key (and diagonals); with key_L0 == L it is the plain call.  Only the inner products' key and diagonal addresses
+ * differ: no copy is made.
+ * HP_EINVAL before anything is enqueued: everything the plain call refuses, key_L0 < L, key_L0 + k > 32, ceil(key_L0/alpha) > 16. */
+int hp_dev_hks_switch_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                         size_t batch, const uint64_t *d_pt, const uint64_t *d_key, uint64_t *d_out);
+int hp_dev_ckks_rotate_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                              size_t batch, size_t step, const uint64_t *d_ct, const uint64_t *d_rot_key, uint64_t *d_out);
+int hp_dev_ckks_conjugate_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                 size_t batch, const uint64_t *d_ct, const uint64_t *d_conj_key, uint64_t *d_out);
+int hp_dev_ckks_rotate_hoisted_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
+                                      const uint64_t *moduli_ext, size_t batch, size_t rotations, const size_t *steps,
+                                      const unsigned char *conj, const uint64_t *d_ct, const uint64_t *const *d_keys, uint64_t *d_out);
+int hp_dev_ckks_lintrans_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                size_t batch, size_t rotations, const size_t *steps, const unsigned char *conj, const uint64_t *d_ct,
+                                const uint64_t *const *d_keys, const uint64_t *const *d_diags, uint64_t *d_out);
+int hp_dev_ckks_lintrans_bsgs_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
+                                     const uint64_t *moduli_ext, size_t batch, size_t babies, const size_t *baby_steps,
+                                     const unsigned char *baby_conj, const uint64_t *const *d_baby_keys, size_t giants,
+                                     const size_t *giant_steps, const unsigned char *giant_conj, const uint64_t *const *d_giant_keys,
+                                     const uint64_t *const *d_diags, const uint64_t *d_ct, uint64_t *d_out);
+int hp_dev_ckks_mult_relin_rescale_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
+                                          const uint64_t *moduli_ext, size_t batch, const uint64_t *d_ct1, const uint64_t *d_ct2,
+                                          const uint64_t *d_key, uint64_t *d_out);
+int hp_dev_ckks_relin_rescale_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
+                                     const uint64_t *moduli_ext, size_t batch, const uint64_t *d_quad, const uint64_t *d_key,
+                                     uint64_t *d_out);
+int hp_dev_ckks_dot_relin_rescale_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
+                                         const uint64_t *moduli_ext, size_t batch, size_t terms, const uint64_t *const *d_a,
+                                         const uint64_t *const *d_b, const uint64_t *d_key, uint64_t *d_out);
 /* Hybrid keys generated on the device.  Sampling stays with the caller: the uniform rows a and the error polynomials e are INPUTS, so
  * a call is deterministic and every output word is pinned by the exact model (tests/test_gpu_hks_keygen.py); what runs here is the
  * arithmetic -- residues of small signed polynomials, batched forward transforms, one streaming multiply-add in Montgomery form.
