@@ -158,6 +158,15 @@ SIGNATURES = {
     "hp_dev_poly_from_signed": (INT, [P, szt, szt, P, szt, P, P]),
     "hp_dev_hks_keygen": (INT, [P, szt, szt, szt, szt, P, szt, P, P, P, P, P]),
     "hp_dev_hks_keygen_rot": (INT, [P, szt, szt, szt, szt, P, szt, P, P, P, P, P, P]),
+    # BGV over the hybrid key switch: the CKKS twin's arguments with plain_modulus after moduli_ext
+    "hp_dev_bgv_hks_switch": (INT, [P, szt, szt, szt, szt, P, u64, szt, P, P, P]),
+    "hp_dev_bgv_rotate_hoisted_hks": (INT, [P, szt, szt, szt, szt, P, u64, szt, szt, P, P, P, P, P]),
+    "hp_dev_bgv_relin_modswitch_hks": (INT, [P, szt, szt, szt, szt, P, u64, szt, P, P, P]),
+    "hp_dev_bgv_mult_relin_modswitch_hks": (INT, [P, szt, szt, szt, szt, P, u64, szt, P, P, P, P]),
+    "hp_dev_bgv_hks_switch_at": (INT, [P, szt, szt, szt, szt, szt, P, u64, szt, P, P, P]),
+    "hp_dev_bgv_rotate_hoisted_hks_at": (INT, [P, szt, szt, szt, szt, szt, P, u64, szt, szt, P, P, P, P, P]),
+    "hp_dev_bgv_relin_modswitch_hks_at": (INT, [P, szt, szt, szt, szt, szt, P, u64, szt, P, P, P]),
+    "hp_dev_bgv_mult_relin_modswitch_hks_at": (INT, [P, szt, szt, szt, szt, szt, P, u64, szt, P, P, P, P]),
     "hp_dev_ckks_rescale_n": (INT, [P, szt, szt, P, szt, szt, P, P, P]),
     "hp_wire_fnv1a64": (u64, [P, szt]),
     "hp_wire_payload_words": (szt, [P]),

@@ -106,17 +106,22 @@ struct HksRotations {
 // key_L0 >= L: the ciphertext moduli the caller's keys (and diagonals) were generated for; the plain entry points are key_L0 == L.
 // It reaches the inner-product launches as KE = key_L0 + k, the rows of one key digit, and nothing else: the plan, the constants,
 // the workspace, the digit stage and ModDown are those of the level's own chain.
+// pmod: the plain modulus of the BGV calls, 0 for CKKS.  It reaches ModDown's conversion kernel (pdown) and nothing else: digits, ModUp,
+// the inner products, the transforms and the drops never see the plaintext.
 struct HksCall {
     hp_ctx *ctx;
     const uint64_t *mext;
     size_t logn, L, key_L0, k, alpha, n = 0, E = 0, KE = 0, nd = 0;
+    uint64_t pmod;
+    HpHksPlain plain;   // t != 0: the constants of k_hks_moddown_t, built by open()
     const Plan *plan = nullptr;
     const HksEntry *he = nullptr;
     std::optional<LevelScope> lvl;
     int rc;
 
-    HksCall(hp_ctx *c, size_t logn_, size_t L_, size_t key_L0_, size_t k_, size_t alpha_, const uint64_t *moduli_ext, size_t batch)
-        : ctx(c), mext(moduli_ext), logn(logn_), L(L_), key_L0(key_L0_), k(k_), alpha(alpha_), rc(limits(batch)) {
+    HksCall(hp_ctx *c, size_t logn_, size_t L_, size_t key_L0_, size_t k_, size_t alpha_, const uint64_t *moduli_ext, size_t batch,
+            uint64_t plain_modulus)
+        : ctx(c), mext(moduli_ext), logn(logn_), L(L_), key_L0(key_L0_), k(k_), alpha(alpha_), pmod(plain_modulus), rc(limits(batch)) {
         if (!rc) n = (size_t)1 << logn, E = L + k, KE = key_L0 + k, nd = (L + alpha - 1) / alpha;
     }
     HksCall(const HksCall &) = delete;   // (one LevelScope per call)
@@ -135,7 +140,30 @@ struct HksCall {
     int open() {
         if ((rc = get_plan(ctx, logn, mext, E, true, &plan)) || (rc = get_hks_consts(ctx, mext, L, k, alpha, &he))) return rc;
         lvl.emplace(ctx, plan);   // level A: the digit stages (lifted digits, coefficient rows) and the drops on the FP64 kernels
+        if (pmod) plain_consts();
         return rc = lvl->rc;
+    }
+    // What a BGV entry point refuses on top of its CKKS sibling, after the shared limits: t must be invertible modulo every modulus
+    // of the chain (they are primes: 0 < t < each of them is enough), and ModDown_t exists as the one-kernel conversion only.
+    int plain_ok() {
+        if (rc) return rc;
+        if (pmod == 0) return rc = fail(ctx, HP_EINVAL, "plain modulus must be positive");
+        for (size_t m = 0; m < L + k; m++)
+            if (pmod >= mext[m]) return rc = fail(ctx, HP_EINVAL, "plain modulus must be below every modulus of the chain");
+        if (k > HP_HKS_MAX_ALPHA) return rc = fail(ctx, HP_EUNSUPPORTED, "more than 8 special primes with a plain modulus");
+        return HP_OK;
+    }
+    void plain_consts() {
+        memset(&plain, 0, sizeof(plain));
+        for (size_t a = 0; a < k; a++) {
+            const u64 p = mext[L + a];
+            plain.tinv_p[a] = hp::inverse_mod_prime(pmod % p, p) % p;
+            plain.tinv_p_h[a] = hp::harvey_quotient(plain.tinv_p[a], p);
+        }
+        for (size_t i = 0; i < L; i++) {
+            plain.t_mod_q[i] = pmod % mext[i];
+            plain.t_mod_q_h[i] = hp::harvey_quotient(plain.t_mod_q[i], mext[i]);
+        }
     }
 
     // The digit stage of P polynomials pt (NTT form, L limbs, row stride pt_pstride): lifted [P][nd][E][N] = every digit's exact
@@ -190,6 +218,11 @@ struct HksCall {
             j.limbs = plan->d_limbs + L;
             if (ctx->cur_a) j.limbs_a = plan->d_limbs_a + L;   // (strict either way: the same words)
             if ((e = run_ntt(ctx, j))) return e;
+        }
+        if (pmod) {   // (k <= HP_HKS_MAX_ALPHA: plain_ok)
+            ProfScope ps(ctx, "hks_moddown_t");
+            return chk(ctx, hp_launch_hks_moddown_t(plan->d_limbs, he->dev, plain, (u32)k, (u32)n, (u32)(2 * P), t.yp, t.rem, ctx->stream),
+                       "hks_moddown_t");
         }
         if (k <= HP_HKS_MAX_ALPHA) {
             ProfScope ps(ctx, "hks_moddown");
@@ -289,17 +322,23 @@ static int no_overlap(hp_ctx *ctx, const char *call, const void *in, size_t in_b
 
 // Every call that takes a key is written once, as its _at form (a key generated for key_L0 >= L ciphertext moduli; hehub_amd.h has
 // the row map); the plain entry point is the case key_L0 == L of the same code.
-extern "C" int hp_dev_hks_switch_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *moduli_ext,
-                                    size_t batch, const uint64_t *pt, const uint64_t *key, uint64_t *out) {
+// The calls that exist for both schemes are written once more: bgv_t == NULL is the CKKS call, else *bgv_t is the plain modulus of
+// its BGV twin (hp_dev_bgv_*_hks), whose own refusals (HksCall::plain_ok) come right after the limits the two share.
+static int dev_hks_switch(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                          const uint64_t *bgv_t, size_t batch, const uint64_t *pt, const uint64_t *key, uint64_t *out) {
     HP_ENTER(ctx);
     HP_REQUIRE(ctx, moduli_ext, pt, key, out);
     HP_ALIGNED(ctx, pt, key, out);
-    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch);
-    if (c.rc || c.open()) return c.rc;
+    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch, bgv_t ? *bgv_t : 0);
+    if (c.rc || (bgv_t && c.plain_ok()) || c.open()) return c.rc;
     int rc = ws_reserve(ctx, c.switch_words(batch) * 8);
     if (rc) return rc;
     Carver cv(ctx->ws);
     return c.key_switch(batch, pt, L, key, Addend(), out, cv);
+}
+extern "C" int hp_dev_hks_switch_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                    size_t batch, const uint64_t *pt, const uint64_t *key, uint64_t *out) {
+    return dev_hks_switch(ctx, logn, L, key_L0, k, alpha, moduli_ext, nullptr, batch, pt, key, out);
 }
 extern "C" int hp_dev_hks_switch(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t batch,
                       const uint64_t *pt, const uint64_t *key, uint64_t *out) {
@@ -312,7 +351,7 @@ static int dev_hks_automorphism(hp_ctx *ctx, size_t logn, size_t L, size_t key_L
     HP_ENTER(ctx);
     HP_REQUIRE(ctx, mext, ct, key, out);
     HP_ALIGNED(ctx, ct, key, out);
-    HksCall c(ctx, logn, L, key_L0, k, alpha, mext, batch);
+    HksCall c(ctx, logn, L, key_L0, k, alpha, mext, batch, 0);
     if (c.rc) return c.rc;
     if (!conj && step >= ((size_t)1 << 17)) return fail(ctx, HP_EINVAL, "rotation step out of range");
     if (c.open()) return c.rc;
@@ -351,14 +390,14 @@ extern "C" int hp_dev_ckks_conjugate_hks_at(hp_ctx *ctx, size_t logn, size_t L, 
 // The rotations are processed HOIST_POLYS / batch at a time (at least one, at most one argument table) against the same digit
 // rows: the working set of a pass is that of an unhoisted rotation of HOIST_POLYS ciphertexts, whatever `rotations` is.
 constexpr size_t HOIST_POLYS = 32;
-extern "C" int hp_dev_ckks_rotate_hoisted_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
-                                                 const uint64_t *moduli_ext, size_t batch, size_t rotations, const size_t *steps,
-                                                 const unsigned char *conj, const uint64_t *ct, const uint64_t *const *keys, uint64_t *out) {
+static int dev_rotate_hoisted_hks(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                  const uint64_t *bgv_t, size_t batch, size_t rotations, const size_t *steps, const unsigned char *conj,
+                                  const uint64_t *ct, const uint64_t *const *keys, uint64_t *out) {
     HP_ENTER(ctx);
     HP_REQUIRE(ctx, moduli_ext, steps, ct, keys, out);
     HP_ALIGNED(ctx, ct, out);
-    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch);
-    if (c.rc) return c.rc;
+    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch, bgv_t ? *bgv_t : 0);
+    if (c.rc || (bgv_t && c.plain_ok())) return c.rc;
     if (rotations == 0) return fail(ctx, HP_EINVAL, "rotate_hoisted: no rotations");
     const HksRotations rot = {rotations, steps, conj, keys};
     int rc = rotations_ok(ctx, "rotate_hoisted", rot, nullptr, false);
@@ -410,6 +449,11 @@ extern "C" int hp_dev_ckks_rotate_hoisted_hks_at(hp_ctx *ctx, size_t logn, size_
     }
     return HP_OK;
 }
+extern "C" int hp_dev_ckks_rotate_hoisted_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
+                                                 const uint64_t *moduli_ext, size_t batch, size_t rotations, const size_t *steps,
+                                                 const unsigned char *conj, const uint64_t *ct, const uint64_t *const *keys, uint64_t *out) {
+    return dev_rotate_hoisted_hks(ctx, logn, L, key_L0, k, alpha, moduli_ext, nullptr, batch, rotations, steps, conj, ct, keys, out);
+}
 extern "C" int hp_dev_ckks_rotate_hoisted_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
                                               size_t batch, size_t rotations, const size_t *steps, const unsigned char *conj,
                                               const uint64_t *ct, const uint64_t *const *keys, uint64_t *out) {
@@ -431,7 +475,7 @@ extern "C" int hp_dev_ckks_lintrans_hks_at(hp_ctx *ctx, size_t logn, size_t L, s
     HP_ENTER(ctx);
     HP_REQUIRE(ctx, moduli_ext, steps, ct, keys, diags, out);
     HP_ALIGNED(ctx, ct, out);
-    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch);
+    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch, 0);
     if (c.rc) return c.rc;
     if (rotations == 0) return fail(ctx, HP_EINVAL, "lintrans: no rotations");
     const HksRotations rot = {rotations, steps, conj, keys};
@@ -487,7 +531,7 @@ extern "C" int hp_dev_ckks_lintrans_bsgs_hks_at(hp_ctx *ctx, size_t logn, size_t
     HP_ENTER(ctx);
     HP_REQUIRE(ctx, moduli_ext, baby_steps, baby_keys, giant_steps, giant_keys, diags, ct, out);
     HP_ALIGNED(ctx, ct, out);
-    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch);
+    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch, 0);
     if (c.rc) return c.rc;
     if (babies == 0 || giants == 0) return fail(ctx, HP_EINVAL, "lintrans_bsgs: no baby steps or no giant steps");
     const HksRotations baby_rot = {babies, baby_steps, baby_conj, baby_keys}, giant_rot = {giants, giant_steps, giant_conj, giant_keys};
@@ -649,7 +693,7 @@ extern "C" int hp_dev_ckks_mult_relin_rescale_hks_at(hp_ctx *ctx, size_t logn, s
     HP_ENTER(ctx);
     HP_REQUIRE(ctx, moduli_ext, ct1, ct2, key, out);
     HP_ALIGNED(ctx, ct1, ct2, key, out);
-    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch);
+    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch, 0);
     if (c.rc) return c.rc;
     if (L < 2) return fail(ctx, HP_EINVAL, "Unable to drop the only one prime.");
     if (c.open()) return c.rc;
@@ -678,7 +722,7 @@ extern "C" int hp_dev_ckks_relin_rescale_hks_at(hp_ctx *ctx, size_t logn, size_t
     HP_ENTER(ctx);
     HP_REQUIRE(ctx, moduli_ext, d_quad, d_key, d_out);
     HP_ALIGNED(ctx, d_quad, d_key, d_out);
-    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch);
+    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch, 0);
     if (c.rc) return c.rc;
     if (L < 2) return fail(ctx, HP_EINVAL, "Unable to drop the only one prime.");
     int rc = no_overlap(ctx, "relin_rescale", d_quad, batch * 3 * L * c.n * 8, d_out, batch * 2 * (L - 1) * c.n * 8);
@@ -758,7 +802,7 @@ extern "C" int hp_dev_ckks_dot_relin_rescale_hks_at(hp_ctx *ctx, size_t logn, si
     HP_ENTER(ctx);
     HP_REQUIRE(ctx, moduli_ext, d_a, d_b, d_key, d_out);
     HP_ALIGNED(ctx, d_key, d_out);
-    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch);
+    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch, 0);
     if (c.rc) return c.rc;
     if (L < 2) return fail(ctx, HP_EINVAL, "Unable to drop the only one prime.");
     const size_t n = c.n;
@@ -778,6 +822,94 @@ extern "C" int hp_dev_ckks_dot_relin_rescale_hks(hp_ctx *ctx, size_t logn, size_
                                                  size_t batch, size_t terms, const uint64_t *const *d_a, const uint64_t *const *d_b,
                                                  const uint64_t *d_key, uint64_t *d_out) {
     return hp_dev_ckks_dot_relin_rescale_hks_at(ctx, logn, L, L, k, alpha, moduli_ext, batch, terms, d_a, d_b, d_key, d_out);
+}
+
+// ---- BGV over the hybrid path --------------------------------------------------------------------------------------------------------
+// Only ModDown knows the scheme (HksCall::pmod, k_hks_moddown_t; hehub_amd.h has the convention): the switch and the hoisted rotations
+// are their CKKS twins with the plain modulus handed on, and a multiplication is the tensor product, the switch of d2 with (d0, d1) as
+// its addend, then hehub's own mod_drop_one_prime_inplace (drop_last with bgv = true: its q_last mod t factor included) -- the
+// two-step composition of relin_rescale above.  ModDown_t and the mod switch are NOT merged into one transform: that path is CKKS's.
+extern "C" int hp_dev_bgv_hks_switch_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                        uint64_t plain_modulus, size_t batch, const uint64_t *pt, const uint64_t *key, uint64_t *out) {
+    return dev_hks_switch(ctx, logn, L, key_L0, k, alpha, moduli_ext, &plain_modulus, batch, pt, key, out);
+}
+extern "C" int hp_dev_bgv_hks_switch(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                     uint64_t plain_modulus, size_t batch, const uint64_t *pt, const uint64_t *key, uint64_t *out) {
+    return dev_hks_switch(ctx, logn, L, L, k, alpha, moduli_ext, &plain_modulus, batch, pt, key, out);
+}
+extern "C" int hp_dev_bgv_rotate_hoisted_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
+                                                const uint64_t *moduli_ext, uint64_t plain_modulus, size_t batch, size_t rotations,
+                                                const size_t *steps, const unsigned char *conj, const uint64_t *ct,
+                                                const uint64_t *const *keys, uint64_t *out) {
+    return dev_rotate_hoisted_hks(ctx, logn, L, key_L0, k, alpha, moduli_ext, &plain_modulus, batch, rotations, steps, conj, ct, keys, out);
+}
+extern "C" int hp_dev_bgv_rotate_hoisted_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                             uint64_t plain_modulus, size_t batch, size_t rotations, const size_t *steps,
+                                             const unsigned char *conj, const uint64_t *ct, const uint64_t *const *keys, uint64_t *out) {
+    return dev_rotate_hoisted_hks(ctx, logn, L, L, k, alpha, moduli_ext, &plain_modulus, batch, rotations, steps, conj, ct, keys, out);
+}
+
+// quad [batch][3][L][N], words below 2q -> out [batch][2][L-1][N] on an open BGV call; the workspace is relin_rescale_words'
+static int bgv_relin_modswitch(const HksCall &c, size_t batch, const u64 *quad, const u64 *key, u64 *out, Carver &cv) {
+    const size_t L = c.L, n = c.n;
+    u64 *lin = cv.take(batch * 2 * L * n);
+    int rc = c.key_switch(batch, quad + 2 * L * n, 3 * L, key, Addend(quad, L, 3 * L, 3), lin, cv);
+    if (rc) return rc;
+    return drop_last(c.ctx, c.plan, c.logn, L, 2 * batch, true, c.pmod, lin, Addend(), out, cv);
+}
+
+// The tail on the caller's quadratic ciphertexts -- hp_dev_mult_low_level's, or a sum of products by hp_dev_ckks_tensor_sum, whose
+// arithmetic is scheme-free (residues of sums of products: nothing in it is CKKS's): T products pay one switch and one mod switch.
+extern "C" int hp_dev_bgv_relin_modswitch_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
+                                                 const uint64_t *moduli_ext, uint64_t plain_modulus, size_t batch, const uint64_t *d_quad,
+                                                 const uint64_t *d_key, uint64_t *d_out) {
+    HP_ENTER(ctx);
+    HP_REQUIRE(ctx, moduli_ext, d_quad, d_key, d_out);
+    HP_ALIGNED(ctx, d_quad, d_key, d_out);
+    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch, plain_modulus);
+    if (c.rc) return c.rc;
+    if (L < 2) return fail(ctx, HP_EINVAL, "Unable to drop the only one prime.");
+    if (c.plain_ok()) return c.rc;
+    int rc = no_overlap(ctx, "bgv_relin_modswitch", d_quad, batch * 3 * L * c.n * 8, d_out, batch * 2 * (L - 1) * c.n * 8);
+    if (rc) return rc;
+    if (c.open()) return c.rc;
+    if ((rc = ws_reserve(ctx, relin_rescale_words(c, batch) * 8))) return rc;
+    Carver cv(ctx->ws);
+    return bgv_relin_modswitch(c, batch, d_quad, d_key, d_out, cv);
+}
+extern "C" int hp_dev_bgv_relin_modswitch_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                              uint64_t plain_modulus, size_t batch, const uint64_t *d_quad, const uint64_t *d_key,
+                                              uint64_t *d_out) {
+    return hp_dev_bgv_relin_modswitch_hks_at(ctx, logn, L, L, k, alpha, moduli_ext, plain_modulus, batch, d_quad, d_key, d_out);
+}
+
+// bgv::mult_low_level + relinearisation with a hybrid key + mod switch: the tensor product into a workspace quad, then the tail
+extern "C" int hp_dev_bgv_mult_relin_modswitch_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
+                                                      const uint64_t *moduli_ext, uint64_t plain_modulus, size_t batch, const uint64_t *ct1,
+                                                      const uint64_t *ct2, const uint64_t *key, uint64_t *out) {
+    HP_ENTER(ctx);
+    HP_REQUIRE(ctx, moduli_ext, ct1, ct2, key, out);
+    HP_ALIGNED(ctx, ct1, ct2, key, out);
+    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch, plain_modulus);
+    if (c.rc) return c.rc;
+    if (L < 2) return fail(ctx, HP_EINVAL, "Unable to drop the only one prime.");
+    if (c.plain_ok() || c.open()) return c.rc;
+    const size_t n = c.n;
+    int rc = ws_reserve(ctx, (padded(batch * 3 * L * n) / 8 + relin_rescale_words(c, batch)) * 8);
+    if (rc) return rc;
+    Carver cv(ctx->ws);
+    u64 *quad = cv.take(batch * 3 * L * n);
+    {
+        ProfScope ps(ctx, "tensor");
+        if ((rc = chk(ctx, hp_launch_tensor(c.plan->d_limbs, (u32)L, 0, (u32)L, (u32)n, (u32)batch, ct1, ct2, quad, ctx->stream), "tensor")))
+            return rc;
+    }
+    return bgv_relin_modswitch(c, batch, quad, key, out, cv);
+}
+extern "C" int hp_dev_bgv_mult_relin_modswitch_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                                   uint64_t plain_modulus, size_t batch, const uint64_t *ct1, const uint64_t *ct2,
+                                                   const uint64_t *key, uint64_t *out) {
+    return hp_dev_bgv_mult_relin_modswitch_hks_at(ctx, logn, L, L, k, alpha, moduli_ext, plain_modulus, batch, ct1, ct2, key, out);
 }
 
 // ---- key generation ----------------------------------------------------------------------------------------------------------------
@@ -816,7 +948,7 @@ extern "C" int hp_dev_poly_from_signed(hp_ctx *ctx, size_t logn, size_t L, const
 static int dev_hks_keygen(hp_ctx *ctx, const char *call, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *mext, size_t keys,
                           const HksRotations *rot, const uint64_t *d_s_to, const uint64_t *d_from, const uint64_t *d_a, const int64_t *d_e,
                           uint64_t *d_keys) {
-    HksCall c(ctx, logn, L, L, k, alpha, mext, keys);
+    HksCall c(ctx, logn, L, L, k, alpha, mext, keys, 0);
     if (c.rc) return c.rc;
     const size_t n = c.n, E = c.E, nd = c.nd, chunks = keygen_chunks(n);
     int rc;

@@ -12,6 +12,7 @@
 //            when m belongs to digit d -- the same 128-bit accumulation as hehub's inner product
 //   ModDown  the P-part of the result, centred exactly (hp_edge.hip: k_base_to_single_crt), is subtracted and the rest
 //            multiplied by P^-1:  out = (x - NTT(rem)) * P^-1 [+ addend]
+//            BGV (a plain modulus t): the remainder is t * centre([x]_P t^-1 mod P), so that the quotient keeps x's value mod t
 //   keygen   the keys themselves from the caller's samples: key_d = ((NTT(e) - a s_to + [digit d] (P mod q) s_from) 2^64, a 2^64)
 // Tile skeleton, launch helpers and the Garner digits shared with hp_edge.hip: hp_elem.h.
 #include "hp_elem.h"
@@ -553,6 +554,58 @@ hipError_t hp_launch_hks_moddown(const HpLimb *limbs, const HpHksConsts *hc, u32
                                  hipStream_t stream) {
     return elem_with_1to8(k, [&](auto kk) {
         return elem_launch(k_hks_moddown<decltype(kk)::value>, P2, n, stream, limbs, hc, n, ElemChunks{}, yp, rem);
+    });
+}
+
+// ModDown with a plain modulus t (BGV; hehub_amd.h has the convention): the remainder is delta = t * c, c the centred value of
+// u = [x]_P * t^-1 mod P -- delta = x mod P, delta = 0 mod t, |delta| <= t (P + 1) / 2 -- so that (x - delta) / P keeps x's value mod t.
+// k_hks_moddown with two multiplications more: every special-prime residue by t^-1 mod p_a (strict) before the Garner digits, the
+// centred residue by t mod q_m (Harvey, strict: the representative q_m of 0 becomes 0) before the store.  Words below q_m: what
+// down() and the fused drops take from k_hks_moddown.  The t-dependent constants are the by-value argument pc -- HpHksConsts
+// belongs to the chain alone.  Register budget (tests/test_hks_bgv_resources.py): no scratch, and the occupancy of k_hks_moddown<K>.
+template <int K>
+__global__ void __launch_bounds__(ELEM_THREADS) k_hks_moddown_t(const HpLimb *__restrict__ limbs, const HpHksConsts *__restrict__ hc,
+                                                              HpHksPlain pc, u32 n, u32 chunks, const u64 *__restrict__ yp,
+                                                              u64 *__restrict__ rem) {
+    const u32 L = hc->L;
+    const ElemTile tile(n, chunks);   // row = p2
+    const u32 p2 = tile.row;
+    const u64 *src = yp + (size_t)p2 * K * n;
+    u64 *dst = rem + (size_t)p2 * L * n;
+    for (const u32 i : tile.words()) {
+        // K >= 4: the Garner tables are read anew for every word (scalar loads, the constant cache) rather than hoisted out of this
+        // loop and spilled -- with pc's words on top of k_hks_moddown's that costs a wave per SIMD at K = 4 and scratch from K = 6 on
+        if constexpr (K >= 4) asm volatile("" : "+s"(hc));
+        u64 v[K][1];
+#pragma unroll
+        for (int a = 0; a < K; a++) {
+            const u64 pa = limbs[L + a].q;
+            v[a][0] = hp_strict(hp_harvey_lazy(src[(size_t)a * n + i], pc.tinv_p[a], pc.tinv_p_h[a], pa), pa);
+            garner_digit<K>(v[a], v, a, pa, limbs[L + a].barrett_c, hc->pg_inv, hc->pg_inv_h);
+        }
+        const bool below = garner_below<K>(v, 0, K, hc->p_half);
+        for (u32 m = 0; m < L; m++) {
+            const u64 qm = limbs[m].q;
+            u64 r = 0;
+#pragma unroll
+            for (int a = 0; a < K; a++) {
+                r += hp_strict(hp_harvey_lazy(v[a][0], hc->p_pref[m][a], hc->p_pref_h[m][a], qm), qm);
+                r -= (r >= qm) ? qm : 0;
+            }
+            if (!below) {
+                u64 abs = hc->p_mod_q[m] + qm - r;
+                abs -= (abs >= qm) ? qm : 0;
+                r = qm - abs;
+            }
+            dst[(size_t)m * n + i] = hp_strict(hp_harvey_lazy(r, pc.t_mod_q[m], pc.t_mod_q_h[m], qm), qm);
+        }
+    }
+}
+
+hipError_t hp_launch_hks_moddown_t(const HpLimb *limbs, const HpHksConsts *hc, const HpHksPlain &pc, u32 k, u32 n, u32 P2, const u64 *yp,
+                                   u64 *rem, hipStream_t stream) {
+    return elem_with_1to8(k, [&](auto kk) {
+        return elem_launch(k_hks_moddown_t<decltype(kk)::value>, P2, n, stream, limbs, hc, pc, n, ElemChunks{}, yp, rem);
     });
 }
 

@@ -231,6 +231,14 @@ struct HpHksConsts {   // device memory, built by the engine per (moduli, k, alp
 // yp [P2][k][n] (strict coefficients of the special-prime part) -> rem [P2][L][n]: the exact centred value in every q_i
 hipError_t hp_launch_hks_moddown(const HpLimb *limbs, const HpHksConsts *hc, u32 k, u32 n, u32 P2, const u64 *yp, u64 *rem,
                                  hipStream_t stream);
+// ModDown with a plain modulus t (BGV): rem = t * centre( [x]_P * t^-1 mod P ) in every q_i, canonical residues; k <= HP_HKS_MAX_ALPHA.
+// What depends on t travels by value, built per call on the host: HpHksConsts stays a function of the chain.
+struct HpHksPlain {
+    u64 tinv_p[HP_HKS_MAX_ALPHA], tinv_p_h[HP_HKS_MAX_ALPHA];   // t^-1 mod p_a (+ Harvey word)
+    u64 t_mod_q[HP_MAX_LIMBS], t_mod_q_h[HP_MAX_LIMBS];         // t mod q_i (+ Harvey word)
+};
+hipError_t hp_launch_hks_moddown_t(const HpLimb *limbs, const HpHksConsts *hc, const HpHksPlain &pc, u32 k, u32 n, u32 P2, const u64 *yp,
+                                   u64 *rem, hipStream_t stream);
 hipError_t hp_launch_hks_modup(const HpLimb *limbs, const HpHksConsts *hc, u32 alpha, u32 nd, u32 n, u32 P, const u64 *coef,
                                u64 *lifted, hipStream_t stream);
 // The inner products.  KE >= E: the rows of one digit of every key (and of every diagonal) they read -- E for a key of this chain;

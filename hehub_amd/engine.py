@@ -554,6 +554,45 @@ class Engine:
                   self._ptr(key), self._ptr(out))
         return out
 
+    # -- BGV over the hybrid key switch: t = the plain modulus; keys are hks_keygen's / hks_keygen_rot's for error rows t * e ----------
+    def bgv_hks_switch(self, moduli_ext, t: int, k: int, alpha: int, pt, key, out=None, key_L0=None):
+        """hks_switch with the plain-modulus ModDown: pt [B][L][n] -> [B][2][L][n], out0 + out1 s_to = pt s_from + t * (small)"""
+        B, L, n = pt.shape
+        out = self.empty((B, 2, L, n)) if out is None else out
+        self._hks("hp_dev_bgv_hks_switch", key_L0, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), t, B, self._ptr(pt),
+                  self._ptr(key), self._ptr(out))
+        return out
+
+    def bgv_rotate_hoisted_hks(self, moduli_ext, t: int, k: int, alpha: int, ct, keys, steps, conj=None, out=None, key_L0=None):
+        """ckks_rotate_hoisted_hks for BGV ciphertexts: the cycle by steps[r] rotates the two slot rows, conj[r] swaps them
+        -> [B][R][2][L][n].  One rotation is a list of one."""
+        B, _, L, n = ct.shape
+        R = len(keys)
+        assert len(steps) == R and (conj is None or len(conj) == R)
+        out = self.empty((B, R, 2, L, n)) if out is None else out
+        kp = (capi.P * R)(*[None if key is None else key.data_ptr() for key in keys])
+        st = (C.c_size_t * R)(*[int(s) for s in steps])
+        cj = (C.c_ubyte * R)(*[1 if c else 0 for c in conj]) if conj is not None else None
+        self._hks("hp_dev_bgv_rotate_hoisted_hks", key_L0, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), t, B, R, st, cj,
+                  self._ptr(ct), kp, self._ptr(out))
+        return out
+
+    def bgv_relin_modswitch_hks(self, moduli_ext, t: int, k: int, alpha: int, quad, key, out=None, key_L0=None):
+        """quad [B][3][L][n] (mult_low_level's or ckks_tensor_sum's) -> hybrid relinearisation + BGV mod switch, [B][2][L-1][n]"""
+        B, _, L, n = quad.shape
+        out = self.empty((B, 2, max(L - 1, 1), n)) if out is None else out
+        self._hks("hp_dev_bgv_relin_modswitch_hks", key_L0, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), t, B,
+                  self._ptr(quad), self._ptr(key), self._ptr(out))
+        return out
+
+    def bgv_mult_hks(self, moduli_ext, t: int, k: int, alpha: int, ct1, ct2, key, out=None, key_L0=None):
+        """bgv::mult with a hybrid relinearisation key + mod switch by the last ciphertext modulus -> [B][2][L-1][n]"""
+        B, _, L, n = ct1.shape
+        out = self.empty((B, 2, max(L - 1, 1), n)) if out is None else out
+        self._hks("hp_dev_bgv_mult_relin_modswitch_hks", key_L0, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), t, B,
+                  self._ptr(ct1), self._ptr(ct2), self._ptr(key), self._ptr(out))
+        return out
+
     def poly_from_signed(self, moduli, coeffs):
         """small signed polynomials, coeffs [B][n] (any int64 values, device tensor) -> NTT form [B][L][n]: the words hp_dev_ntt produces
         from the strict residues.  How a ternary secret or an error polynomial gets to the device."""

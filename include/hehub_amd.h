@@ -685,6 +685,65 @@ int hp_dev_hks_keygen(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha
 int hp_dev_hks_keygen_rot(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t keys,
                           const size_t *steps, const unsigned char *conj, const uint64_t *d_s /* u64[L+k][N] */,
                           const uint64_t *d_a, const int64_t *d_e, uint64_t *d_keys);
+/* BGV over the hybrid key switch.  hehub's bgv::relinearize pays L*L digit transforms, carries the noise of one special prime and runs
+ * its inner switch with plain modulus 1; it has no rotation.  Of the hybrid path only ModDown knows the scheme -- digits, ModUp, the
+ * inner products, hoisting and the _at key addressing never see the plaintext -- so the calls below are their CKKS twins with one
+ * other conversion kernel.  plain_modulus = t comes directly after moduli_ext, as in hp_dev_bgv_mult_relin_modswitch.
+ *
+ * The convention (pinned by tests/hks_bgv_model.py).  P = p_0...p_{k-1}; ModDown_t takes the accumulator x over the basis Q P and,
+ * for every coefficient,
+ *     u = ([x]_P * t^-1) mod P                        0 <= u < P
+ *     c = u  if u < floor(P/2),  u - P  otherwise     (the centring of the CKKS ModDown)
+ *     delta = t * c                                   delta = x mod P,  delta = 0 mod t,  |delta| <= t (P + 1) / 2
+ *     ModDown_t(x) = (x - delta) / P   mod every q_i
+ * NO factor (P mod t) follows: a key encrypts (P mod q_i) * s_from with error t * e, so x = P * (c1 s_from) + t E and
+ * (x - delta) / P = c1 s_from (mod t) exactly.  (hehub's mod switch multiplies by q_last mod t because it divides the message
+ * itself; the two mod-switch calls below end with exactly that drop.)  t = 1 gives the residues of the CKKS ModDown.
+ * Keys: a BGV hybrid key is the output of hp_dev_hks_keygen / hp_dev_hks_keygen_rot, unchanged, for the error rows d_e = t * e --
+ * the rows are int64_t, so t * e is one multiplication by the caller; a relinearisation key is s_from = s * s.
+ * Contract as for every hybrid call: on residues, every output word below 2 q_i, parity level A follows the context; the workspace is
+ * that of the CKKS call of the same shape.  Each call has its _at twin (key_L0 after L, the rule above).
+ * Refused before anything is enqueued: everything the corresponding CKKS call refuses, with its code; plain_modulus == 0 or
+ * plain_modulus >= any modulus of moduli_ext (HP_EINVAL: the moduli are primes, so t is then invertible everywhere); k > 8
+ * (HP_EUNSUPPORTED: the conversion by one composition per modulus is not extended); L < 2 for the two mod-switch calls (HP_EINVAL).
+ * Out of scope: ModDown_t merged with the mod switch into one transform (the fast path of hp_dev_ckks_mult_relin_rescale_hks stays
+ * CKKS-only); BGV forms of the diagonal / BSGS transforms and of the fused dot call; the node and sharded layers; the C++ host layer,
+ * which has no hybrid calls at all.
+ *
+ * hp_dev_bgv_hks_switch: hp_dev_hks_switch with ModDown_t.  d_pt u64[batch][L][N] -> d_out u64[batch][2][L][N], and with a key for
+ * error rows t * e:  out0 + out1 * s_to = pt * s_from + t * (small)  (mod Q). */
+int hp_dev_bgv_hks_switch(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                          uint64_t plain_modulus, size_t batch, const uint64_t *d_pt, const uint64_t *d_key, uint64_t *d_out);
+int hp_dev_bgv_hks_switch_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                             uint64_t plain_modulus, size_t batch, const uint64_t *d_pt, const uint64_t *d_key, uint64_t *d_out);
+/* hp_dev_bgv_rotate_hoisted_hks: the arguments, the digit sharing, the signed-digit property and the refusals of
+ * hp_dev_ckks_rotate_hoisted_hks (steps / conj / d_keys are HOST arrays): one digit stage per ciphertext, one ModDown_t per rotation;
+ * a single rotation is rotations == 1.  On the BGV slots (two rows of N/2) the cycle by `step` rotates both rows, the involution
+ * (conj[r] != 0) swaps them.  d_out u64[batch][rotations][2][L][N]. */
+int hp_dev_bgv_rotate_hoisted_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                  uint64_t plain_modulus, size_t batch, size_t rotations, const size_t *steps, const unsigned char *conj,
+                                  const uint64_t *d_ct, const uint64_t *const *d_keys, uint64_t *d_out);
+int hp_dev_bgv_rotate_hoisted_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
+                                     const uint64_t *moduli_ext, uint64_t plain_modulus, size_t batch, size_t rotations,
+                                     const size_t *steps, const unsigned char *conj, const uint64_t *d_ct,
+                                     const uint64_t *const *d_keys, uint64_t *d_out);
+/* hp_dev_bgv_relin_modswitch_hks: d_quad u64[batch][3][L][N], words below 2q -> d_out u64[batch][2][L-1][N]: the hybrid switch of d2
+ * with (d0, d1) as its addend, then hehub's mod_drop_one_prime_inplace (the drop of hp_dev_bgv_mod_switch, its q_last mod t factor
+ * included).  d_quad is hp_dev_mult_low_level's, or a sum of products by hp_dev_ckks_tensor_sum -- whose arithmetic is scheme-free
+ * despite its name: T products then pay one switch and one mod switch.  d_out must not overlap d_quad. */
+int hp_dev_bgv_relin_modswitch_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                   uint64_t plain_modulus, size_t batch, const uint64_t *d_quad, const uint64_t *d_key, uint64_t *d_out);
+int hp_dev_bgv_relin_modswitch_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
+                                      const uint64_t *moduli_ext, uint64_t plain_modulus, size_t batch, const uint64_t *d_quad,
+                                      const uint64_t *d_key, uint64_t *d_out);
+/* hp_dev_bgv_mult_relin_modswitch_hks: the tensor product into a workspace quad, then the tail above: on the same operands the words
+ * of hp_dev_mult_low_level followed by hp_dev_bgv_relin_modswitch_hks. */
+int hp_dev_bgv_mult_relin_modswitch_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                        uint64_t plain_modulus, size_t batch, const uint64_t *d_ct1, const uint64_t *d_ct2,
+                                        const uint64_t *d_key, uint64_t *d_out);
+int hp_dev_bgv_mult_relin_modswitch_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
+                                           const uint64_t *moduli_ext, uint64_t plain_modulus, size_t batch, const uint64_t *d_ct1,
+                                           const uint64_t *d_ct2, const uint64_t *d_key, uint64_t *d_out);
 /* ct u64[batch][2][L][N] -> out u64[batch][2][L-drops][N]; d_tmp: 2 * batch*2*(L-1)*N words (may be NULL for drops == 1) */
 int hp_dev_ckks_rescale_n(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, size_t drops, size_t batch,
                           const uint64_t *d_ct, uint64_t *d_tmp, uint64_t *d_out);
