@@ -158,6 +158,13 @@ SIGNATURES = {
     "hp_dev_poly_from_signed": (INT, [P, szt, szt, P, szt, P, P]),
     "hp_dev_hks_keygen": (INT, [P, szt, szt, szt, szt, P, szt, P, P, P, P, P]),
     "hp_dev_hks_keygen_rot": (INT, [P, szt, szt, szt, szt, P, szt, P, P, P, P, P, P]),
+    # device sampling (seed: 32 host bytes; stream: the 64-bit polynomial id) and the key generators over it
+    "hp_dev_sample_uniform": (INT, [P, szt, szt, P, P, szt, P, u64, szt, P]),
+    "hp_dev_sample_ternary": (INT, [P, szt, szt, P, u64, P]),
+    "hp_dev_sample_cbd": (INT, [P, szt, szt, P, u64, P]),
+    "hp_dev_hks_keygen_seeded": (INT, [P, szt, szt, szt, szt, P, szt, P, P, P, u64, u64, P]),
+    "hp_dev_hks_keygen_rot_seeded": (INT, [P, szt, szt, szt, szt, P, szt, P, P, P, P, u64, u64, P]),
+    "hp_dev_hks_key_expand": (INT, [P, szt, szt, szt, szt, P, szt, P, u64, P]),
     # BGV over the hybrid key switch: the CKKS twin's arguments with plain_modulus after moduli_ext
     "hp_dev_bgv_hks_switch": (INT, [P, szt, szt, szt, szt, P, u64, szt, P, P, P]),
     "hp_dev_bgv_rotate_hoisted_hks": (INT, [P, szt, szt, szt, szt, P, u64, szt, szt, P, P, P, P, P]),

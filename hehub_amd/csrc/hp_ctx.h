@@ -5,6 +5,7 @@
 //   hp_api_scheme.cpp  key switch, drop-last-prime, relinearisation, rotations, the mult pipelines, limb-range stages
 //   hp_api_hks.cpp     hybrid key switch (extension)
 //   hp_drop.cpp        the constants of the fused drop launches (hp_drop.h: HpDropArgs field by field); host only, no HIP, no context
+//   hp_sample_host.cpp the device samplers' rules on the host (hp_sample.h: the ChaCha20 stream layout); host only, for the tests
 //   hp_node.cpp        several contexts (GPUs) behind one handle: batch slices and the limb-sharded exchange
 // There is NO CPU fallback anywhere: every entry point launches HIP kernels or fails.
 #pragma once

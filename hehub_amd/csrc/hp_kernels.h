@@ -3,6 +3,7 @@
 #pragma once
 #include "hp_device.h"
 #include "hp_drop.h"   // HP_MAX_LIMBS, HpDropConsts, HpDropArgs, HpInvMixArgs
+#include "hp_sample.h" // HpSampleSeed, the kind tags
 
 // ---- transform jobs -----------------------------------------------------------
 // A transform launch processes W independent limb transforms ("work items").
@@ -305,3 +306,17 @@ hipError_t hp_launch_hks_combine(const HpLimb *limbs, const HpHksConsts *hc, u32
 hipError_t hp_launch_hks_down_fin(const HpLimb *limbs, const HpHksConsts *hc, u32 L, u32 n, u32 P2, const u64 *x, const u64 *rem,
                                   const u64 *addend, u32 add_poly_stride, u32 add_ct_stride, u32 add_mask, u64 *out,
                                   hipStream_t stream);
+// device samplers (hp_sample.hip; hp_sample.h has the stream layout).  One thread per ChaCha20 block of 8 words, at most
+// HP_SAMPLE_MAX_BLOCKS workgroups of 256 threads to a launch.
+// uniform: polynomial b < batch (id stream_id + b), row m < L (modulus rows.q[m], label rows.id[m]) -> out + b * stride + m * N, canonical
+// residues; mont_limbs != NULL (the plan of the same moduli): every word times 2^64 mod q instead, canonical.  logn >= 3.
+#define HP_SAMPLE_MAX_BLOCKS ((u64)1 << 30)
+struct HpSampleRows {
+    u64 q[HP_MAX_LIMBS];
+    unsigned char id[HP_MAX_LIMBS];
+};
+hipError_t hp_launch_sample_uniform(const HpSampleSeed &seed, const HpSampleRows &rows, const HpLimb *mont_limbs, u32 L, u32 logn, u64 batch,
+                                    u64 stream_id, u64 stride, u64 *out, hipStream_t stream);
+// kind HP_SAMPLE_TERNARY / HP_SAMPLE_CBD: out [batch][N] = scale * the sample of id stream_id + b
+hipError_t hp_launch_sample_signed(u32 kind, const HpSampleSeed &seed, u32 logn, u64 batch, u64 stream_id, long long scale, long long *out,
+                                   hipStream_t stream);

@@ -632,6 +632,67 @@ class Engine:
                                                  None if a is None else self._ptr(a), self._ptr(e), self._ptr(out)))
         return out
 
+    # -- device sampling: everything a function of (seed: 32 bytes, stream: 64-bit polynomial id) ----
+    @staticmethod
+    def _seed(seed: bytes):
+        if len(seed) != 32:
+            raise InvalidArgument(capi.HP_EINVAL, "a sampling seed is 32 bytes")
+        return (C.c_ubyte * 32).from_buffer_copy(bytes(seed))
+
+    def sample_uniform(self, logn: int, moduli, seed: bytes, stream: int, batch: int = 1, limb_ids=None, out=None, stride_words: int = 0):
+        """uniform residues -> [batch][L][n], canonical words, directly as NTT-form rows; polynomial b has the id stream + b, row m the
+        label limb_ids[m] (default m).  out with stride_words: polynomial b goes to out + b * stride_words words, the gaps untouched."""
+        L, n = len(moduli), 1 << logn
+        assert (out is None) == (stride_words == 0)
+        out = self.empty((batch, L, n)) if out is None else out
+        ids = None if limb_ids is None else (C.c_uint32 * L)(*[int(i) for i in limb_ids])
+        self._chk(self.lib.hp_dev_sample_uniform(self.h, logn, L, _u64arr(moduli), ids, batch, self._seed(seed), stream, stride_words,
+                                                 self._ptr(out)))
+        return out
+
+    def sample_ternary(self, logn: int, seed: bytes, stream: int, batch: int = 1):
+        """ternary coefficients in {-1, 0, 1} -> int64 [batch][n] (poly_from_signed turns them into a secret's rows)"""
+        out = self.empty((batch, 1 << logn))
+        self._chk(self.lib.hp_dev_sample_ternary(self.h, logn, batch, self._seed(seed), stream, self._ptr(out)))
+        return out
+
+    def sample_cbd(self, logn: int, seed: bytes, stream: int, batch: int = 1):
+        """centred binomial coefficients, eta = 21 (range +-21, variance 10.5) -> int64 [batch][n]"""
+        out = self.empty((batch, 1 << logn))
+        self._chk(self.lib.hp_dev_sample_cbd(self.h, logn, batch, self._seed(seed), stream, self._ptr(out)))
+        return out
+
+    def hks_keygen_seeded(self, moduli_ext, k: int, alpha: int, s_to, s_from, seed: bytes, stream: int, error_scale: int = 1, out=None):
+        """hks_keygen on rows drawn on the device: for key r, digit d, a = the uniform sample and e = error_scale * the centred-binomial
+        sample of the polynomial id stream + r * dnum + d.  s_to [E][n], s_from [R][E][n] -> [R][dnum][2][E][n]."""
+        R, E, n = s_from.shape
+        nd = (E - k + alpha - 1) // alpha
+        out = self.empty((R, nd, 2, E, n)) if out is None else out
+        self._chk(self.lib.hp_dev_hks_keygen_seeded(self.h, n.bit_length() - 1, E - k, k, alpha, _u64arr(moduli_ext), R, self._ptr(s_to),
+                                                    self._ptr(s_from), self._seed(seed), stream, error_scale, self._ptr(out)))
+        return out
+
+    def hks_keygen_rot_seeded(self, moduli_ext, k: int, alpha: int, s, steps, seed: bytes, stream: int, error_scale: int = 1, conj=None,
+                              out=None):
+        """hks_keygen_rot on rows drawn on the device (ids as for hks_keygen_seeded): s [E][n] -> [len(steps)][dnum][2][E][n]"""
+        E, n = s.shape
+        R = len(steps)
+        assert conj is None or len(conj) == R
+        nd = (E - k + alpha - 1) // alpha
+        out = self.empty((R, nd, 2, E, n)) if out is None else out
+        st = (C.c_size_t * R)(*[int(x) for x in steps])
+        cj = (C.c_ubyte * R)(*[1 if c else 0 for c in conj]) if conj is not None else None
+        self._chk(self.lib.hp_dev_hks_keygen_rot_seeded(self.h, n.bit_length() - 1, E - k, k, alpha, _u64arr(moduli_ext), R, st, cj,
+                                                        self._ptr(s), self._seed(seed), stream, error_scale, self._ptr(out)))
+        return out
+
+    def hks_key_expand(self, moduli_ext, k: int, alpha: int, keys, seed: bytes, stream: int):
+        """keys [R][dnum][2][E][n] whose [0] halves are loaded: the [1] halves are rewritten from (seed, stream), in place"""
+        R, nd, _, E, n = keys.shape
+        self._chk(self.lib.hp_dev_hks_key_expand(self.h, n.bit_length() - 1, E - k, k, alpha, _u64arr(moduli_ext), R, self._seed(seed),
+                                                 stream, self._ptr(keys)))
+        return keys
+
     def ckks_rescale_n(self, moduli, ct, drops: int):
         B, _, L, n = ct.shape
         out = self.empty((B, 2, L - drops, n))

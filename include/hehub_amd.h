@@ -649,7 +649,8 @@ int hp_dev_ckks_relin_rescale_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t 
 int hp_dev_ckks_dot_relin_rescale_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
                                          const uint64_t *moduli_ext, size_t batch, size_t terms, const uint64_t *const *d_a,
                                          const uint64_t *const *d_b, const uint64_t *d_key, uint64_t *d_out);
-/* Hybrid keys generated on the device.  Sampling stays with the caller: the uniform rows a and the error polynomials e are INPUTS, so
+/* Hybrid keys generated on the device.  In the three calls below the uniform rows a and the error polynomials e are INPUTS (the
+ * seeded forms further down draw them on the device, hp_dev_sample_*), so
  * a call is deterministic and every output word is pinned by the exact model (tests/test_gpu_hks_keygen.py); what runs here is the
  * arithmetic -- residues of small signed polynomials, batched forward transforms, one streaming multiply-add in Montgomery form.
  * None of the three calls needs workspace: the error rows are spread into d_keys[r][d][0] and transformed there in place.
@@ -685,6 +686,59 @@ int hp_dev_hks_keygen(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha
 int hp_dev_hks_keygen_rot(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t keys,
                           const size_t *steps, const unsigned char *conj, const uint64_t *d_s /* u64[L+k][N] */,
                           const uint64_t *d_a, const int64_t *d_e, uint64_t *d_keys);
+/* Sampling on the device: a counter-based ChaCha20 keystream (RFC 8439 section 2.3, 20 rounds) and three samplers over it.  Every
+ * output is a function of (seed, stream) alone -- no generator state, no host draws, nothing crossing PCIe -- and is pinned word for
+ * word by tests/sample_model.py.  (hehub's samplers use a default-seeded std::default_random_engine and double arithmetic that is
+ * not exact above 2^53; they are not reproduced.)
+ *
+ * The stream.  One block yields 16 output words o[0..15] and serves the 8 coefficients 8j .. 8j+7 of one row, so logn >= 3; its state:
+ *     words 0-3    the four ChaCha constants
+ *     words 4-11   the 32 seed bytes as little-endian u32
+ *     word  12     the block index j
+ *     word  13     attempt (bits 0-15) | kind << 16 (bits 16-23) | limb_id << 24 (bits 24-31)
+ *     words 14,15  low / high half of the 64-bit polynomial id
+ * Coefficient 8j + c owns the candidate v_c = o[2c] | o[2c+1] << 32 (keystream bytes 8c .. 8c+7, little-endian).  The kind (1 uniform,
+ * 2 ternary, 3 centred binomial) keeps the samplers from sharing keystream under one (seed, stream).  Polynomial b of a call has the
+ * id stream + b in 64-bit arithmetic.
+ *   uniform, modulus q (2 <= q < 2^63): w = v_c & (2^bit_length(q) - 1), accepted when w < q; otherwise the same candidate position
+ *     of the same block under attempt + 1.  Bounded: after 64 rejected attempts (0 .. 63; probability < 2^-64 per word, acceptance
+ *     being at least 1/2) the word is w - q of the last candidate.  The canonical residue; a row is sampled directly as an NTT-form
+ *     row (uniform in either domain).  limb_id is the caller's label of the modulus, by default the row index.
+ *   ternary (limb_id 0, attempt 0): the first of the 32 two-bit fields of v_c, from the low end, that is not 3, minus 1; 0 if all are 3.
+ *   centred binomial, eta = 21 (limb_id 0, attempt 0): popcount(v_c & (2^21 - 1)) - popcount((v_c >> 21) & (2^21 - 1)): range +-21,
+ *     variance 10.5 (sigma 3.24: hehub's default std_dev = 3.2 as an exact integer distribution).
+ *
+ * hp_dev_sample_uniform: row m of polynomial b goes to d_out + b * stride + m * N words, stride = stride_words, or L * N where that
+ * is 0; the words between the rows of two polynomials are not touched (uniform rows can be written straight into d_keys[r][d][1]).
+ * hp_dev_sample_ternary / hp_dev_sample_cbd: i64[batch][N], for hp_dev_poly_from_signed or as error rows.
+ * HP_EINVAL before anything is enqueued: logn < 3 or above 16, L == 0 or L > 32, batch == 0, a modulus < 2 or >= 2^63, a limb id
+ * >= 256, a stride that is odd or below L * N, a NULL seed or moduli, a device pointer that is NULL or not 16-byte aligned.
+ * Out of scope: a wire kind for half keys; sparse / fixed-Hamming-weight secrets; discrete Gaussians; sampling inside the inner
+ * product; the node, sharded and C++ host layers. */
+int hp_dev_sample_uniform(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli,
+                          const uint32_t *limb_ids /* HOST, L entries < 256, NULL = 0..L-1 */, size_t batch,
+                          const uint8_t *seed /* HOST, 32 bytes */, uint64_t stream,
+                          size_t stride_words /* 0 = L*N; else >= L*N and even */, uint64_t *d_out);
+int hp_dev_sample_ternary(hp_ctx *ctx, size_t logn, size_t batch, const uint8_t *seed, uint64_t stream,
+                          int64_t *d_out /* i64[batch][N] */);
+int hp_dev_sample_cbd(hp_ctx *ctx, size_t logn, size_t batch, const uint8_t *seed, uint64_t stream, int64_t *d_out);
+/* The seeded key generators: hp_dev_hks_keygen / hp_dev_hks_keygen_rot on rows drawn here.  For key r, digit d, with the polynomial id
+ * stream + r * dnum + d:  a[r][d] is the uniform sample over all L + k moduli with limb ids 0 .. L+k-1, e[r][d] is error_scale times
+ * the centred-binomial sample (error_scale = 1 for CKKS, = t for BGV, whose keys need error rows t * e).  The key is word for word
+ * what the plain call writes for those rows: the samplers write a into the [1] halves and e into workspace, then the plain call's
+ * in-place path (d_a == NULL) runs.  Workspace: keys * dnum * N words, whatever L and k are.
+ * hp_dev_hks_key_expand rewrites only the [r][d][1] halves (a * 2^64 mod q_m, canonical) from (seed, stream) and leaves the [0]
+ * halves as the caller loaded them: a key set can be stored or shipped as its [0] halves plus 40 bytes.
+ * HP_EINVAL before anything is enqueued: logn < 3, a NULL seed, keys == 0, error_scale == 0 or >= 2^58 (21 * error_scale must fit an
+ * int64_t); then everything the plain call refuses, with its code. */
+int hp_dev_hks_keygen_seeded(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t keys,
+                             const uint64_t *d_s_to, const uint64_t *d_s_from, const uint8_t *seed, uint64_t stream,
+                             uint64_t error_scale, uint64_t *d_keys);
+int hp_dev_hks_keygen_rot_seeded(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t keys,
+                                 const size_t *steps, const unsigned char *conj, const uint64_t *d_s, const uint8_t *seed,
+                                 uint64_t stream, uint64_t error_scale, uint64_t *d_keys);
+int hp_dev_hks_key_expand(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t keys,
+                          const uint8_t *seed, uint64_t stream, uint64_t *d_keys);
 /* BGV over the hybrid key switch.  hehub's bgv::relinearize pays L*L digit transforms, carries the noise of one special prime and runs
  * its inner switch with plain modulus 1; it has no rotation.  Of the hybrid path only ModDown knows the scheme -- digits, ModUp, the
  * inner products, hoisting and the _at key addressing never see the plaintext -- so the calls below are their CKKS twins with one
