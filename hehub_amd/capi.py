@@ -165,6 +165,10 @@ SIGNATURES = {
     "hp_dev_hks_keygen_seeded": (INT, [P, szt, szt, szt, szt, P, szt, P, P, P, u64, u64, P]),
     "hp_dev_hks_keygen_rot_seeded": (INT, [P, szt, szt, szt, szt, P, szt, P, P, P, P, u64, u64, P]),
     "hp_dev_hks_key_expand": (INT, [P, szt, szt, szt, szt, P, szt, P, u64, P]),
+    # fresh ciphertexts from a seed: (kind,) seed, stream, scale as values; with_c1 an int
+    "hp_dev_sample_small_ntt": (INT, [P, szt, szt, P, szt, C.c_uint32, P, u64, u64, P]),
+    "hp_dev_rlwe_encrypt_seeded": (INT, [P, szt, szt, P, szt, P, P, P, u64, u64, INT, P]),
+    "hp_dev_rlwe_encrypt_pk_seeded": (INT, [P, szt, szt, P, szt, P, P, P, u64, u64, P]),
     # BGV over the hybrid key switch: the CKKS twin's arguments with plain_modulus after moduli_ext
     "hp_dev_bgv_hks_switch": (INT, [P, szt, szt, szt, szt, P, u64, szt, P, P, P]),
     "hp_dev_bgv_rotate_hoisted_hks": (INT, [P, szt, szt, szt, szt, P, u64, szt, szt, P, P, P, P, P]),

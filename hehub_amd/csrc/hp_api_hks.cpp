@@ -1158,3 +1158,113 @@ extern "C" int hp_dev_hks_key_expand(hp_ctx *ctx, size_t logn, size_t L, size_t 
     if (c.open()) return c.rc;
     return sample_key_rows(c, keys, seed, stream, true, d_keys);
 }
+
+// ---- fresh ciphertexts from a seed (kernels in hp_sample.hip) ---------------------------------------------------------------------------
+// The small polynomials (errors, the public-key form's u) go from the keystream straight to the residues of every modulus
+// (k_sample_spread) and through the batched forward transform where the ciphertext will lie; one fused kernel then finishes the
+// rows.  The transforms are the level-B launches at either parity level and the last kernel reduces to the canonical residue, so
+// the words do not depend on the level.
+static const char *ENC_SCALE_MSG = "the scale must be positive and below 2^58";
+
+// what the three calls refuse alike, before their own checks; polys = the small polynomials of the call's largest spread launch
+static int enc_seeded_ok(hp_ctx *ctx, const char *call, size_t logn, size_t L, const uint64_t *moduli, size_t batch, size_t polys,
+                         uint64_t scale, HpSampleRows &rows) {
+    int rc = sample_logn_ok(ctx, logn);
+    if (rc) return rc;
+    if (L < 1 || L > HP_MAX_LIMBS) return fail(ctx, HP_EINVAL, "unsupported number of moduli");
+    if (batch == 0) return fail(ctx, HP_EINVAL, "empty batch");
+    if (scale == 0 || scale >= HP_SAMPLE_MAX_SCALE) return fail(ctx, HP_EINVAL, ENC_SCALE_MSG);
+    if ((rc = sample_rows(ctx, L, moduli, nullptr, rows))) return rc;
+    const size_t n = (size_t)1 << logn;
+    if (polys > std::min(sample_max_rows(n), KEYGEN_MAX_BLOCKS / keygen_chunks(n)) / L)
+        return fail(ctx, HP_EUNSUPPORTED, std::string(call) + ": too many polynomials for one call");
+    return HP_OK;
+}
+// `polys` small polynomials (ids stream + p * id_step) as residues into the rows dst + p * pstride_rows * N, transformed in place
+static int small_ntt_rows(hp_ctx *ctx, const Plan *plan, const HpSampleRows &rows, u32 kind, size_t logn, size_t L, size_t polys,
+                          const uint8_t *seed, uint64_t stream, uint64_t id_step, uint64_t scale, size_t pstride_rows, u64 *dst) {
+    int rc;
+    {
+        ProfScope ps(ctx, "sample_spread");
+        if ((rc = chk(ctx, hp_launch_sample_spread(kind, hp_sample_seed(seed), rows, (u32)L, (u32)logn, polys, stream, id_step, (long long)scale,
+                                                   pstride_rows << logn, dst, ctx->stream), "sample_spread")))
+            return rc;
+    }
+    return run_ntt(ctx, batch_job(plan, logn, L, polys, dst, dst, pstride_rows, pstride_rows, 0, 0));
+}
+
+extern "C" int hp_dev_sample_small_ntt(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, size_t batch, uint32_t kind,
+                                       const uint8_t *seed, uint64_t stream, uint64_t scale, uint64_t *d_out) {
+    HP_ENTER(ctx);
+    HP_REQUIRE(ctx, moduli, seed, d_out);
+    HP_ALIGNED(ctx, d_out);
+    if (kind != HP_SAMPLE_TERNARY && kind != HP_SAMPLE_CBD) return fail(ctx, HP_EINVAL, "sample_small_ntt: kind is 2 (ternary) or 3 (centred binomial)");
+    HpSampleRows rows;
+    int rc = enc_seeded_ok(ctx, "sample_small_ntt", logn, L, moduli, batch, batch, scale, rows);
+    if (rc) return rc;
+    const Plan *plan;
+    if ((rc = get_plan(ctx, logn, moduli, L, true, &plan))) return rc;
+    if ((rc = small_ntt_rows(ctx, plan, rows, kind, logn, L, batch, seed, stream, 1, scale, L, d_out))) return rc;
+    ProfScope ps(ctx, "elem");
+    return chk(ctx, hp_launch_sample_canonical(plan->d_limbs, (u32)L, (u32)1 << logn, (u32)(batch * L), d_out, ctx->stream), "sample_canonical");
+}
+
+extern "C" int hp_dev_rlwe_encrypt_seeded(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, size_t batch, const uint64_t *d_sk,
+                                          const uint64_t *d_pt, const uint8_t *seed, uint64_t stream, uint64_t error_scale, int with_c1,
+                                          uint64_t *d_ct) {
+    HP_ENTER(ctx);
+    HP_REQUIRE(ctx, moduli, seed, d_sk, d_ct);
+    HP_ALIGNED(ctx, d_sk, d_pt, d_ct);
+    if (with_c1 != 0 && with_c1 != 1) return fail(ctx, HP_EINVAL, "rlwe_encrypt_seeded: with_c1 is 0 or 1");
+    HpSampleRows rows;
+    int rc = enc_seeded_ok(ctx, "rlwe_encrypt_seeded", logn, L, moduli, batch, batch, error_scale, rows);
+    if (rc) return rc;
+    const size_t n = (size_t)1 << logn, ct_rows = (with_c1 ? 2 : 1) * L, ct_bytes = batch * ct_rows * n * 8;
+    if ((rc = no_overlap(ctx, "rlwe_encrypt_seeded", d_sk, L * n * 8, d_ct, ct_bytes)) ||
+        (d_pt && (rc = no_overlap(ctx, "rlwe_encrypt_seeded", d_pt, batch * L * n * 8, d_ct, ct_bytes))))
+        return rc;
+    const Plan *plan;
+    if ((rc = get_plan(ctx, logn, moduli, L, true, &plan))) return rc;
+    // NTT(pt): into the c1 rows where the ciphertext has them (k_enc_seeded reads a word before it stores a over it), else workspace
+    u64 *ptn = nullptr;
+    size_t pt_rows = 0;
+    if (d_pt && with_c1) {
+        ptn = d_ct + L * n;
+        pt_rows = 2 * L;
+    } else if (d_pt) {
+        if ((rc = ws_reserve(ctx, padded(batch * L * n)))) return rc;
+        ptn = Carver(ctx->ws).take(batch * L * n);
+        pt_rows = L;
+    }
+    if ((rc = small_ntt_rows(ctx, plan, rows, HP_SAMPLE_CBD, logn, L, batch, seed, stream, 1, error_scale, ct_rows, d_ct))) return rc;
+    if (d_pt && (rc = run_ntt(ctx, batch_job(plan, logn, L, batch, d_pt, ptn, L, pt_rows, 0, 0)))) return rc;
+    ProfScope ps(ctx, "enc_seeded");
+    return chk(ctx, hp_launch_enc_seeded(hp_sample_seed(seed), rows, plan->d_limbs, (u32)L, (u32)logn, batch, stream, d_sk, ptn, pt_rows * n,
+                                         with_c1 != 0, d_ct, ctx->stream), "enc_seeded");
+}
+
+extern "C" int hp_dev_rlwe_encrypt_pk_seeded(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, size_t batch, const uint64_t *d_pk,
+                                             const uint64_t *d_pt, const uint8_t *seed, uint64_t stream, uint64_t error_scale, uint64_t *d_ct) {
+    HP_ENTER(ctx);
+    HP_REQUIRE(ctx, moduli, seed, d_pk, d_ct);
+    HP_ALIGNED(ctx, d_pk, d_pt, d_ct);
+    HpSampleRows rows;
+    int rc = enc_seeded_ok(ctx, "rlwe_encrypt_pk_seeded", logn, L, moduli, batch, 2 * batch, error_scale, rows);
+    if (rc) return rc;
+    const size_t n = (size_t)1 << logn, ct_bytes = batch * 2 * L * n * 8;
+    if ((rc = no_overlap(ctx, "rlwe_encrypt_pk_seeded", d_pk, 2 * L * n * 8, d_ct, ct_bytes)) ||
+        (d_pt && (rc = no_overlap(ctx, "rlwe_encrypt_pk_seeded", d_pt, batch * L * n * 8, d_ct, ct_bytes))))
+        return rc;
+    const Plan *plan;
+    if ((rc = get_plan(ctx, logn, moduli, L, true, &plan))) return rc;
+    if ((rc = ws_reserve(ctx, (d_pt ? 2 : 1) * padded(batch * L * n)))) return rc;
+    Carver cv(ctx->ws);
+    u64 *u = cv.take(batch * L * n), *ptn = d_pt ? cv.take(batch * L * n) : nullptr;
+    // e0_b, e1_b: the ids stream + 2b, stream + 2b + 1 -- the 2 * batch polynomials of d_ct in order; u_b: the ternary sample of stream + 2b
+    if ((rc = small_ntt_rows(ctx, plan, rows, HP_SAMPLE_CBD, logn, L, 2 * batch, seed, stream, 1, error_scale, L, d_ct)) ||
+        (rc = small_ntt_rows(ctx, plan, rows, HP_SAMPLE_TERNARY, logn, L, batch, seed, stream, 2, 1, L, u)))
+        return rc;
+    if (d_pt && (rc = run_ntt(ctx, batch_job(plan, logn, L, batch, d_pt, ptn, L, L, 0, 0)))) return rc;
+    ProfScope ps(ctx, "enc_pk_fin");
+    return chk(ctx, hp_launch_enc_pk_fin(plan->d_limbs, (u32)L, (u32)n, (u32)batch, d_pk, u, ptn, d_ct, ctx->stream), "enc_pk_fin");
+}

@@ -320,3 +320,18 @@ hipError_t hp_launch_sample_uniform(const HpSampleSeed &seed, const HpSampleRows
 // kind HP_SAMPLE_TERNARY / HP_SAMPLE_CBD: out [batch][N] = scale * the sample of id stream_id + b
 hipError_t hp_launch_sample_signed(u32 kind, const HpSampleSeed &seed, u32 logn, u64 batch, u64 stream_id, long long scale, long long *out,
                                    hipStream_t stream);
+// fresh ciphertexts.  spread: kind HP_SAMPLE_TERNARY / HP_SAMPLE_CBD; polynomial p < batch (id stream_id + p * id_step), row m < L ->
+// out + p * pstride + m * N = the canonical residues of scale * the sample modulo rows.q[m], coefficient form (rows.id is not read)
+hipError_t hp_launch_sample_spread(u32 kind, const HpSampleSeed &seed, const HpSampleRows &rows, u32 L, u32 logn, u64 batch, u64 stream_id,
+                                   u64 id_step, long long scale, u64 pstride, u64 *out, hipStream_t stream);
+// ciphertext b < batch at ct + b * (with_c1 ? 2 : 1) * L * N, its c0 rows holding NTT(e_b) on entry (lazy transform words):
+// c0 = NTT(e) + ptn - a * sk, canonical, a = the uniform sample of id stream_id + b (labels rows.id), written to the c1 rows only
+// with_c1.  ptn: rows ptn + b * pt_stride + m * N (lazy transform words; with_c1 they may be the c1 rows), or NULL: zero.  sk [L][N] < 2q
+hipError_t hp_launch_enc_seeded(const HpSampleSeed &seed, const HpSampleRows &rows, const HpLimb *limbs, u32 L, u32 logn, u64 batch, u64 stream_id,
+                                const u64 *sk, const u64 *ptn, u64 pt_stride, bool with_c1, u64 *ct, hipStream_t stream);
+// ct [P][2][L][n] holding NTT(e0), NTT(e1) on entry; pk [2][L][n] < 2q; u, ptn [P][L][n] lazy transform words (ptn may be NULL)
+//   -> ct[p] = (pk0 * u + e0 + ptn, pk1 * u + e1), canonical
+hipError_t hp_launch_enc_pk_fin(const HpLimb *limbs, u32 L, u32 n, u32 P, const u64 *pk, const u64 *u, const u64 *ptn, u64 *ct,
+                                hipStream_t stream);
+// x [rows][n] lazy transform words -> canonical residues in place, limb of a row = row % L
+hipError_t hp_launch_sample_canonical(const HpLimb *limbs, u32 L, u32 n, u32 rows, u64 *x, hipStream_t stream);

@@ -112,8 +112,26 @@ constexpr int64_t hp_sample_cbd_word(u64 v) {
     return (int64_t)__builtin_popcountll(v & m) - (int64_t)__builtin_popcountll(v >> HP_SAMPLE_ETA & m);
 }
 
+// ---- a scaled small coefficient as the canonical residue modulo q (k_sample_spread, hp_dev_sample_small_ntt) ---------------------------------
+// v = scale * (a ternary or binomial word), |v| <= 21 * scale < 2^63: the magnitude modulo q, then the conditional negation q - r,
+// where r = 0 stays 0 (hp_dev_poly_from_signed's rule).  The magnitude is below q whenever 21 * scale < q -- the usual case, no
+// division; either way the same word.
+constexpr u64 hp_sample_residue(int64_t v, u64 q) {
+    const bool neg = v < 0;
+    const u64 a = neg ? (u64)0 - (u64)v : (u64)v;
+    const u64 r = a < q ? a : a % q;
+    return (neg && r) ? q - r : r;
+}
+constexpr int64_t hp_sample_small_word(u32 kind, u64 candidate) {
+    return kind == HP_SAMPLE_TERNARY ? hp_sample_ternary_word(candidate) : hp_sample_cbd_word(candidate);
+}
+
 // ---- the samplers on the host (hp_sample_host.cpp): what the kernels of hp_sample.hip write, word for word --------------------------------------
 namespace hpi {
+// kind: HP_SAMPLE_TERNARY or HP_SAMPLE_CBD; out [batch][L][N]: hp_sample_residue of scale * the sample of id stream + b * id_step in
+// every modulus -- the coefficient rows k_sample_spread writes, before the transform
+void sample_small_host(u32 kind, size_t logn, size_t L, const u64 *moduli, size_t batch, const uint8_t *seed, u64 stream, u64 id_step,
+                       int64_t scale, u64 *out);
 // polynomial b of a call has the id stream + b; row m of it (modulus moduli[m], label limb_ids[m], or m where limb_ids == NULL)
 // goes to out + b * stride_words + m * N
 void sample_uniform_host(size_t logn, size_t L, const u64 *moduli, const u32 *limb_ids, size_t batch, const uint8_t *seed, u64 stream,

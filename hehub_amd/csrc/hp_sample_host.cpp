@@ -39,4 +39,20 @@ void sample_signed_host(u32 kind, size_t logn, size_t batch, const uint8_t *seed
         }
 }
 
+void sample_small_host(u32 kind, size_t logn, size_t L, const u64 *moduli, size_t batch, const uint8_t *seed, u64 stream, u64 id_step,
+                       int64_t scale, u64 *out) {
+    const size_t n = (size_t)1 << logn;
+    const HpSampleSeed sd = hp_sample_seed(seed);
+    for (size_t b = 0; b < batch; b++)
+        for (size_t j = 0; j < n / 8; j++) {
+            u32 st[16] = {}, o[16] = {};
+            hp_sample_state(sd, (u32)j, hp_sample_word13(0, kind, 0), stream + b * id_step, st);
+            hp_chacha20_block(st, o, HpRotl{});
+            for (u32 c = 0; c < 8; c++) {
+                const int64_t v = scale * hp_sample_small_word(kind, hp_sample_candidate(o, c));
+                for (size_t m = 0; m < L; m++) out[(b * L + m) * n + 8 * j + c] = hp_sample_residue(v, moduli[m]);
+            }
+        }
+}
+
 } // namespace hpi

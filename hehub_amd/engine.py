@@ -693,6 +693,43 @@ class Engine:
                                                  stream, self._ptr(keys)))
         return keys
 
+    def sample_small_ntt(self, logn: int, moduli, kind: int, seed: bytes, stream: int, batch: int = 1, scale: int = 1, out=None):
+        """kind 2 (ternary) or 3 (centred binomial): scale * the sample of the polynomial id stream + b, in NTT form -> [batch][L][n],
+        canonical words (poly_from_signed of the sampled rows, reduced), without the int64 rows.  A secret from 40 bytes."""
+        L = len(moduli)
+        out = self.empty((batch, L, 1 << logn)) if out is None else out
+        self._chk(self.lib.hp_dev_sample_small_ntt(self.h, logn, L, _u64arr(moduli), batch, kind, self._seed(seed), stream, scale,
+                                                   self._ptr(out)))
+        return out
+
+    def rlwe_encrypt_seeded(self, moduli, sk, pt, seed: bytes, stream: int, error_scale: int = 1, with_c1: bool = True, batch=None,
+                            out=None):
+        """secret-key encryption on rows drawn on the device: sk [L][n] (NTT form), pt [B][L][n] (coefficient form) or None (zero; then
+        `batch` ciphertexts).  Ciphertext b: a = the uniform, e = error_scale * the centred-binomial sample of the id stream + b;
+        -> [B][2][L][n] = (e + pt - a s, a), or with_c1 = False [B][L][n]: c0 alone, the ciphertext being c0 + (seed, stream).
+        pt = None with c1 is a public key (e - a s, a).  Canonical words."""
+        L, n = sk.shape
+        B = pt.shape[0] if pt is not None else (1 if batch is None else batch)
+        assert pt is None or batch is None or batch == B
+        out = self.empty((B, 2, L, n) if with_c1 else (B, L, n)) if out is None else out
+        self._chk(self.lib.hp_dev_rlwe_encrypt_seeded(self.h, n.bit_length() - 1, L, _u64arr(moduli), B, self._ptr(sk),
+                                                      None if pt is None else self._ptr(pt), self._seed(seed), stream, error_scale,
+                                                      1 if with_c1 else 0, self._ptr(out)))
+        return out
+
+    def rlwe_encrypt_pk_seeded(self, moduli, pk, pt, seed: bytes, stream: int, error_scale: int = 1, batch=None, out=None):
+        """public-key encryption: pk [2][L][n] (rlwe_encrypt_seeded with pt = None), pt [B][L][n] (coefficient form) or None.
+        Ciphertext b: u = the ternary sample of the id stream + 2b, e0, e1 = error_scale * the centred-binomial samples of stream + 2b,
+        stream + 2b + 1 -> [B][2][L][n] = (pk0 u + e0 + pt, pk1 u + e1), canonical words.  Ids stream .. stream + 2B - 1."""
+        _, L, n = pk.shape
+        B = pt.shape[0] if pt is not None else (1 if batch is None else batch)
+        assert pt is None or batch is None or batch == B
+        out = self.empty((B, 2, L, n)) if out is None else out
+        self._chk(self.lib.hp_dev_rlwe_encrypt_pk_seeded(self.h, n.bit_length() - 1, L, _u64arr(moduli), B, self._ptr(pk),
+                                                         None if pt is None else self._ptr(pt), self._seed(seed), stream, error_scale,
+                                                         self._ptr(out)))
+        return out
+
     def ckks_rescale_n(self, moduli, ct, drops: int):
         B, _, L, n = ct.shape
         out = self.empty((B, 2, L - drops, n))

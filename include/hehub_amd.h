@@ -275,7 +275,7 @@ int hp_dev_bgv_mult_relin_modswitch_t(hp_ctx *ctx, size_t logn, size_t L, const 
 /* rlwe.cpp:57-72 encrypt_core with the samples of get_rlwe_sample supplied by the caller (sampling stays on the host):
  * noise int64[batch][N] rounded Gaussian integers (lifted per modulus and transformed as sampling.cpp:76-86 does),
  * c1 u64[batch][L][N] uniform NTT-form words, pt u64[batch][L][N] coefficient form, sk u64[L][N] NTT form
- * -> ct u64[batch][2][L][N] */
+ * -> ct u64[batch][2][L][N].  (hp_dev_rlwe_encrypt_seeded, further down, draws the samples on the device from a seed.) */
 int hp_dev_rlwe_encrypt_core(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, size_t batch,
                              const int64_t *d_noise, const uint64_t *d_c1, const uint64_t *d_pt, const uint64_t *d_sk,
                              uint64_t *d_ct);
@@ -739,6 +739,57 @@ int hp_dev_hks_keygen_rot_seeded(hp_ctx *ctx, size_t logn, size_t L, size_t k, s
                                  uint64_t stream, uint64_t error_scale, uint64_t *d_keys);
 int hp_dev_hks_key_expand(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t keys,
                           const uint8_t *seed, uint64_t stream, uint64_t *d_keys);
+/* Fresh ciphertexts from a seed: secrets, public keys, secret-key and public-key encryption drawn on the device from the stream
+ * above.  The contract of the seeded key generators holds for the three calls: every output word is the CANONICAL residue (< q_m),
+ * the same word at either parity level, a function of (seed, stream) and the inputs alone; a refusal comes before anything is
+ * enqueued and leaves the output untouched.  hp_dev_rlwe_encrypt_core (caller's noise and c1 rows, hehub's lazy words) is unchanged.
+ *
+ * hp_dev_sample_small_ntt: kind 2 (ternary) or 3 (centred binomial); polynomial b has the id stream + b.  Row [b][m] holds the
+ * canonical residues of the words hp_dev_poly_from_signed produces from scale * hp_dev_sample_ternary / _cbd(seed, stream + b) --
+ * the same polynomial, reduced below q_m -- without the int64 rows ever reaching memory: one thread turns a block into the
+ * residues of its 8 coefficients in all L moduli (a coefficient v, |v| <= 21 * scale, maps to |v| mod q_m, negated to q_m - r where
+ * v < 0 and r != 0), the forward transform and one reduction follow.  How a secret, or the u of a public-key encryption, gets to
+ * the device from 40 bytes.  The call uses the ids stream .. stream + batch - 1.
+ *
+ * hp_dev_rlwe_encrypt_seeded: for ciphertext b, with the polynomial id stream + b:  a_b = the uniform sample over `moduli` with limb
+ * ids 0 .. L-1, e_b = error_scale times the centred-binomial sample (the kind tag keeps the two apart), and
+ *     c1 = a_b        c0 = NTT(e_b) + NTT(pt_b) - a_b * s      (mod q_m)
+ * error_scale = 1 is the CKKS form, error_scale = t the BGV form t * e - a * s + m.  d_pt is in coefficient form, hp_dev_ntt's input
+ * contract; NULL is the zero plaintext.  The call uses the ids stream .. stream + batch - 1.
+ *   with_c1 == 1: d_ct is u64[batch][2][L][N] = (c0, c1).
+ *   with_c1 == 0: d_ct is u64[batch][L][N], c0 alone -- the ciphertext is c0 plus the 40 bytes (seed, stream), half the bytes to store
+ *     or ship.  There is no expand call: with c0_b copied to the [0] half of ciphertext b,
+ *         hp_dev_sample_uniform(ctx, logn, L, moduli, NULL, batch, seed, stream, 2 * L * N, d_ct + L * N)
+ *     writes exactly the c1 rows of the with_c1 == 1 call.
+ *   d_pt == NULL and with_c1 == 1 is public-key generation, pk = (e - a * s, a), for hp_dev_rlwe_encrypt_pk_seeded; the compressed
+ *     form (with_c1 == 0) is pk0 plus the seed.
+ * a is drawn in registers by the kernel that forms c0: it is never read from memory and, in the compressed form, never written.
+ * Workspace: none when d_pt == NULL or with_c1 == 1 (NTT(pt) passes through the c1 rows); else batch * L * N words.
+ *
+ * hp_dev_rlwe_encrypt_pk_seeded: for ciphertext b:  u_b = the ternary sample of the id stream + 2b, e0_b = error_scale times the
+ * centred-binomial sample of stream + 2b, e1_b = the same of stream + 2b + 1 (the kind tag keeps u_b and e0_b apart), and
+ *     ct0 = pk0 * NTT(u_b) + NTT(e0_b) + NTT(pt_b)        ct1 = pk1 * NTT(u_b) + NTT(e1_b)      (mod q_m)
+ * The call uses the ids stream .. stream + 2 * batch - 1.  With pk = (e_pk - a * s, a) the ciphertext decrypts to pt plus
+ * error_scale * (u * e_pk + e0 + e1 * s) -- pk generated with the same error_scale.  Workspace: at most 2 * batch * L * N words.
+ *
+ * HP_EINVAL before anything is enqueued: logn < 3 or above 16, L == 0 or L > 32, batch == 0 (not the silent HP_OK of
+ * hp_dev_rlwe_encrypt_core), a modulus < 2 or >= 2^63, a NULL seed, moduli, d_sk / d_pk, d_ct or d_out, a device pointer that is not
+ * 16-byte aligned, a scale that is 0 or >= 2^58, a kind outside {2, 3}, with_c1 outside {0, 1}, d_ct overlapping d_sk, d_pk or
+ * d_pt.  Chains that hp_dev_ntt refuses are refused with its code.
+ * Out of scope: a wire kind for seeded ciphertexts; the node, sharded and C++ host layers; CKKS encoding; discrete Gaussians;
+ * regenerating pk1 from a seed inside the public-key call. */
+int hp_dev_sample_small_ntt(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, size_t batch,
+                            uint32_t kind /* 2 ternary, 3 centred binomial */, const uint8_t *seed /* HOST, 32 bytes */,
+                            uint64_t stream, uint64_t scale, uint64_t *d_out /* u64[batch][L][N] */);
+int hp_dev_rlwe_encrypt_seeded(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, size_t batch,
+                               const uint64_t *d_sk /* u64[L][N] NTT form, words < 2 * modulus */,
+                               const uint64_t *d_pt /* u64[batch][L][N] coefficient form; NULL = zero */,
+                               const uint8_t *seed, uint64_t stream, uint64_t error_scale, int with_c1,
+                               uint64_t *d_ct /* with_c1: u64[batch][2][L][N]; else u64[batch][L][N] */);
+int hp_dev_rlwe_encrypt_pk_seeded(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, size_t batch,
+                                  const uint64_t *d_pk /* u64[2][L][N] NTT form, words < 2 * modulus */,
+                                  const uint64_t *d_pt /* as above, may be NULL */, const uint8_t *seed, uint64_t stream,
+                                  uint64_t error_scale, uint64_t *d_ct /* u64[batch][2][L][N] */);
 /* BGV over the hybrid key switch.  hehub's bgv::relinearize pays L*L digit transforms, carries the noise of one special prime and runs
  * its inner switch with plain modulus 1; it has no rotation.  Of the hybrid path only ModDown knows the scheme -- digits, ModUp, the
  * inner products, hoisting and the _at key addressing never see the plaintext -- so the calls below are their CKKS twins with one
