@@ -178,7 +178,14 @@ SIGNATURES = {
     "hp_dev_bgv_rotate_hoisted_hks_at": (INT, [P, szt, szt, szt, szt, szt, P, u64, szt, szt, P, P, P, P, P]),
     "hp_dev_bgv_relin_modswitch_hks_at": (INT, [P, szt, szt, szt, szt, szt, P, u64, szt, P, P, P]),
     "hp_dev_bgv_mult_relin_modswitch_hks_at": (INT, [P, szt, szt, szt, szt, szt, P, u64, szt, P, P, P, P]),
-    "hp_dev_ckks_rescale_n": (INT, [P, szt, szt, P, szt, szt, P, P, P]),
+    # BFV: moduli_qb = q.., b..; the relinearising calls take moduli_ext, then M, aux_moduli, t
+    "hp_dev_bfv_lift": (INT, [P, szt, szt, szt, P, szt, P, P]),
+    "hp_dev_bfv_scale_round": (INT, [P, szt, szt, szt, P, u64, szt, P, P]),
+    "hp_dev_bfv_mult_low_level": (INT, [P, szt, szt, szt, P, u64, szt, P, P, P]),
+    "hp_dev_bfv_mult_relin_hks": (INT, [P, szt, szt, szt, szt, P, szt, P, u64, szt, P, P, P, P]),
+    "hp_dev_bfv_mult_relin_hks_at": (INT, [P, szt, szt, szt, szt, szt, P, szt, P, u64, szt, P, P, P, P]),
+    "hp_dev_bfv_decrypt_round": (INT, [P, szt, szt, P, u64, szt, P, P]),
+    "hp_dev_ckks_rescale_n":(INT, [P, szt, szt, P, szt, szt, P, P, P]),
     "hp_wire_fnv1a64": (u64, [P, szt]),
     "hp_wire_payload_words": (szt, [P]),
     "hp_wire_bytes": (szt, [P]),

@@ -912,6 +912,39 @@ extern "C" int hp_dev_bgv_mult_relin_modswitch_hks(hp_ctx *ctx, size_t logn, siz
     return hp_dev_bgv_mult_relin_modswitch_hks_at(ctx, logn, L, L, k, alpha, moduli_ext, plain_modulus, batch, ct1, ct2, key, out);
 }
 
+// ---- BFV over the hybrid path ----------------------------------------------------------------------------------------------------------
+// BFV's multiplication differs from the others before the switch, not in it: the quadratic ciphertext comes from the scale-invariant
+// product over Q B (bfv_mult, hp_api_bfv.cpp) as canonical residues, and the switch of y2 with (y0, y1) as its addend is the CKKS one
+// (keys with error e, no factor t: the plain ModDown).  The BFV refusals come first, then everything the switch refuses.
+extern "C" int hp_dev_bfv_mult_relin_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                            size_t M, const uint64_t *aux_moduli, uint64_t t, size_t batch, const uint64_t *ct1,
+                                            const uint64_t *ct2, const uint64_t *key, uint64_t *out) {
+    HP_ENTER(ctx);
+    HP_REQUIRE(ctx, moduli_ext, aux_moduli, ct1, ct2, key, out);
+    HP_ALIGNED(ctx, ct1, ct2, key, out);
+    int rc = bfv_check(ctx, logn, L, M, moduli_ext, aux_moduli, true, t, batch);
+    if (rc) return rc;
+    const size_t n = (size_t)1 << logn;
+    if ((rc = no_overlap(ctx, "bfv_mult_relin", ct1, batch * 2 * L * n * 8, out, batch * 2 * L * n * 8)) ||
+        (rc = no_overlap(ctx, "bfv_mult_relin", ct2, batch * 2 * L * n * 8, out, batch * 2 * L * n * 8)))
+        return rc;
+    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch, 0);
+    if (c.rc) return c.rc;
+    BfvShape s;
+    if ((rc = bfv_open(ctx, logn, L, M, moduli_ext, aux_moduli, true, t, s))) return rc;
+    if (c.open()) return c.rc;
+    if ((rc = ws_reserve(ctx, padded(batch * 3 * L * n) + bfv_mult_bytes(s, batch) + c.switch_words(batch) * 8))) return rc;
+    Carver cv(ctx->ws);
+    u64 *quad = cv.take(batch * 3 * L * n);
+    if ((rc = bfv_mult(ctx, s, batch, ct1, ct2, quad, cv))) return rc;
+    return c.key_switch(batch, quad + 2 * L * n, 3 * L, key, Addend(quad, L, 3 * L, 3), out, cv);
+}
+extern "C" int hp_dev_bfv_mult_relin_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t M,
+                                         const uint64_t *aux_moduli, uint64_t t, size_t batch, const uint64_t *ct1, const uint64_t *ct2,
+                                         const uint64_t *key, uint64_t *out) {
+    return hp_dev_bfv_mult_relin_hks_at(ctx, logn, L, L, k, alpha, moduli_ext, M, aux_moduli, t, batch, ct1, ct2, key, out);
+}
+
 // ---- key generation ----------------------------------------------------------------------------------------------------------------
 // The uniform rows a and the error polynomials e are inputs (the caller's, or the device samplers' in the seeded forms further down);
 // what runs here is the arithmetic:

@@ -291,6 +291,25 @@ int get_crt_consts(hp_ctx *ctx, const uint64_t *moduli, size_t L, u64 t, const H
     });
 }
 
+// constants of the BFV conversions (hp_bfv.h: the builders are host-only and tested on the CPU), cached per (moduli_qb, L)
+int get_bfv_consts(hp_ctx *ctx, const uint64_t *moduli_qb, size_t L, size_t M, const HpBfvConsts **out) {
+    return contained(ctx, [&] {
+        auto key = std::make_pair(std::vector<u64>(moduli_qb, moduli_qb + L + M), L);
+        auto it = ctx->bfv.find(key);
+        if (it == ctx->bfv.end()) {
+            int rc = make_room(ctx, ctx->bfv, MAX_BFV);
+            if (rc) return rc;
+            std::vector<HpBfvConsts> hold(1);
+            if (!bfv_build_consts(moduli_qb, L, M, hold[0])) return fail(ctx, HP_EINVAL, "moduli are not pairwise coprime");
+            HpBfvConsts *d = nullptr;
+            if ((rc = upload(ctx, hold.data(), sizeof(HpBfvConsts), (void **)&d))) return rc;
+            it = ctx->bfv.emplace(key, d).first;
+        }
+        *out = it->second;
+        return (int)HP_OK;
+    });
+}
+
 // The workspace only grows.  Replacing it frees memory that kernels enqueued earlier -- on ANY stream this context was
 // pointed at -- may still use, so the whole device is drained first (growth is rare: once per new largest shape).
 // A HIP graph captured earlier holds the old pointers: ws_generation tells the caller that it went stale.
@@ -492,6 +511,7 @@ void hp_ctx_destroy(hp_ctx *ctx) {
             for (auto &kv : sh->perms) (void)hipFree(kv.second);
             for (auto &kv : sh->crt) (void)hipFree(kv.second);
             for (auto &kv : sh->hks) (void)hipFree(kv.second.dev);
+            for (auto &kv : sh->bfv) (void)hipFree(kv.second);
             if (sh->range_flag) (void)hipFree(sh->range_flag);
         }
         if (ctx->ws) (void)hipFree(ctx->ws);

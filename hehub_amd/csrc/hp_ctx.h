@@ -4,6 +4,7 @@
 //   hp_api_poly.cpp    drop-in host entry points, device-resident polynomial batches, encrypt / decrypt cores, base conversions
 //   hp_api_scheme.cpp  key switch, drop-last-prime, relinearisation, rotations, the mult pipelines, limb-range stages
 //   hp_api_hks.cpp     hybrid key switch (extension)
+//   hp_api_bfv.cpp     BFV: exact lift / scale-and-round / multiplication over Q B, decryption rounding (extension)
 //   hp_drop.cpp        the constants of the fused drop launches (hp_drop.h: HpDropArgs field by field); host only, no HIP, no context
 //   hp_sample_host.cpp the device samplers' rules on the host (hp_sample.h: the ChaCha20 stream layout); host only, for the tests
 //   hp_node.cpp        several contexts (GPUs) behind one handle: batch slices and the limb-sharded exchange
@@ -47,7 +48,7 @@ struct ProfEvent {
 };
 
 // caches of small device objects are bounded: when one is full it is emptied (after a device synchronise), not grown
-constexpr size_t MAX_PERMS = 1024, MAX_CRT = 128, MAX_HKS = 16;
+constexpr size_t MAX_PERMS = 1024, MAX_CRT = 128, MAX_HKS = 16, MAX_BFV = 32;
 
 // hybrid key switch constants of one (extended moduli, (k, alpha)): the device block, and what the host needs of it per call
 struct HksEntry {
@@ -72,6 +73,7 @@ struct Shared {
     std::map<std::pair<size_t, size_t>, u32 *> perms;                 // (logn, step mod N/2) -> gather map
     std::map<std::pair<std::vector<u64>, u64>, HpCrtConsts *> crt;    // (old moduli, new modulus) -> CRT-branch constants
     HksCache hks;                                                     // (extended moduli, (k, alpha))
+    std::map<std::pair<std::vector<u64>, size_t>, HpBfvConsts *> bfv; // (moduli_qb, L) -> BFV conversion constants (M = the rest; 0: decryption)
     // level A range guard (hp_ntt_a.hip: RangeAcc): one sticky device word for the family.  Every member keeps its OWN "a level-A call
     // of mine has not been checked yet" state (hp_ctx::a_pending) and reads the word after a synchronisation of its OWN stream; a
     // non-zero word is counted here (`range_trips`) and cleared, and every member that had level-A work pending when a trip was
@@ -84,7 +86,7 @@ struct Shared {
 struct hp_ctx {
     hpi::Shared *sh;
     explicit hp_ctx(hpi::Shared *s)
-        : sh(s), mu(s->mu), tables(s->tables), tables_a(s->tables_a), plans(s->plans), perms(s->perms), crt(s->crt), hks(s->hks) {}
+        : sh(s), mu(s->mu), tables(s->tables), tables_a(s->tables_a), plans(s->plans), perms(s->perms), crt(s->crt), hks(s->hks), bfv(s->bfv) {}
     int device = 0;
     hipStream_t own_stream = nullptr;
     hipStream_t stream = nullptr;
@@ -106,6 +108,7 @@ struct hp_ctx {
     std::map<std::pair<size_t, size_t>, u32 *> &perms;
     std::map<std::pair<std::vector<u64>, u64>, HpCrtConsts *> &crt;
     hpi::HksCache &hks;
+    std::map<std::pair<std::vector<u64>, size_t>, HpBfvConsts *> &bfv;
     void *ws = nullptr;
     size_t ws_bytes = 0;
     unsigned long ws_generation = 0;   // bumped whenever the workspace is reallocated or released (captured graphs go stale)
@@ -236,6 +239,8 @@ struct LevelScope {
 int get_cycle_perm(hp_ctx *ctx, size_t logn, size_t step, const u32 **out);
 int reserve_cycle_perms(hp_ctx *ctx, size_t count);   // the next `count` get_cycle_perm calls do not empty the cache
 int get_crt_consts(hp_ctx *ctx, const uint64_t *moduli, size_t L, u64 t, const HpCrtConsts **out);
+// BFV conversion constants of (moduli_qb, L, M) (hp_bfv.h); M == 0: what the decryption rounding reads.  HP_EINVAL: not pairwise coprime
+int get_bfv_consts(hp_ctx *ctx, const uint64_t *moduli_qb, size_t L, size_t M, const HpBfvConsts **out);
 
 // ---- workspace --------------------------------------------------------------------------------------------
 // grow-only scratch; stream order makes reuse across calls safe (hp_ctx_set_stream orders streams, see hp_ctx.cpp)
@@ -283,5 +288,23 @@ int drop_last(hp_ctx *ctx, const Plan *plan, size_t logn, size_t L, size_t P2, b
               u64 *out, Carver &cv);
 // moved = the automorphism of ct [rows][n]: the involution (conj), or the cycle by `step`
 int move_rows(hp_ctx *ctx, size_t logn, size_t rows, bool conj, size_t step, const u64 *ct, u64 *moved);
+
+// ---- BFV on an open shape (hp_api_bfv.cpp), also used by the relinearising calls of hp_api_hks.cpp ----
+struct BfvShape {
+    size_t logn = 0, L = 0, M = 0, n = 0;
+    std::vector<u64> qb;   // q_0 .. q_{L-1}, b_0 .. b_{M-1}
+    u64 t = 0;
+    const Plan *plan = nullptr;   // of qb, with transforms
+    const HpBfvConsts *consts = nullptr;
+    HpBfvPlain plain;
+};
+// every refusal of the BFV calls that depends on (logn, L, M, q, b, t, count) alone, in the order hehub_amd.h lists them
+// (with_t: the call has a plain modulus -- the lift has none, and no base-size rule with it)
+int bfv_check(hp_ctx *ctx, size_t logn, size_t L, size_t M, const uint64_t *q, const uint64_t *b, bool with_t, u64 t, size_t count);
+// the plan of q.., b.. and the constants of a shape that bfv_check has passed
+int bfv_open(hp_ctx *ctx, size_t logn, size_t L, size_t M, const uint64_t *q, const uint64_t *b, bool with_t, u64 t, BfvShape &s);
+size_t bfv_mult_bytes(const BfvShape &s, size_t batch);
+// ct1, ct2 [batch][2][L][N] (words below 2q) -> quad [batch][3][L][N], canonical residues
+int bfv_mult(hp_ctx *ctx, const BfvShape &s, size_t batch, const u64 *ct1, const u64 *ct2, u64 *quad, Carver &cv);
 
 } // namespace hpi

@@ -4,6 +4,7 @@
 #include "hp_device.h"
 #include "hp_drop.h"   // HP_MAX_LIMBS, HpDropConsts, HpDropArgs, HpInvMixArgs
 #include "hp_sample.h" // HpSampleSeed, the kind tags
+#include "hp_bfv.h"    // HpBfvBase, HpBfvConsts, HpBfvPlain, HpBfvDecPlain
 
 // ---- transform jobs -----------------------------------------------------------
 // A transform launch processes W independent limb transforms ("work items").
@@ -306,6 +307,22 @@ hipError_t hp_launch_hks_combine(const HpLimb *limbs, const HpHksConsts *hc, u32
 hipError_t hp_launch_hks_down_fin(const HpLimb *limbs, const HpHksConsts *hc, u32 L, u32 n, u32 P2, const u64 *x, const u64 *rem,
                                   const u64 *addend, u32 add_poly_stride, u32 add_ct_stride, u32 add_mask, u64 *out,
                                   hipStream_t stream);
+// ---- BFV (extension; hp_bfv.hip, constants in hp_bfv.h) ------------------------------------------------------------
+// exact centred conversion: src [P][src_ps rows][n], strict coefficient rows modulo the cnt moduli of the plan xs -> dst [P][dst_ps
+// rows][n], row m = the canonical residue modulo ys[m] (T of them) of x below floor(X/2), of x - X from there on.  cnt <= HP_BFV_MAX
+static_assert(HP_BFV_MAX == HP_CRT_MAX_LIMBS && 2 * HP_BFV_MAX == HP_MAX_LIMBS, "hp_bfv.h counts in the engine's limits");
+hipError_t hp_launch_bfv_lift(const HpLimb *xs, const HpLimb *ys, const HpBfvBase *bc, u32 cnt, u32 T, u32 n, u32 P, const u64 *src,
+                              u32 src_ps, u64 *dst, u32 dst_ps, hipStream_t stream);
+// src [P][L + M][n] strict coefficient rows over moduli_qb (plan limbs) -> y [P][M][n] = floor((t x + h) / Q) modulo every b_j, canonical
+hipError_t hp_launch_bfv_scale(const HpLimb *limbs, const HpBfvConsts *bc, const HpBfvPlain &pc, u32 L, u32 n, u32 P, const u64 *src, u64 *y,
+                               hipStream_t stream);
+// x [P][L][n] strict coefficient rows -> out [P][n] = floor((t x + h) / Q) mod t; bc: the constants of (moduli, L, M = 0)
+hipError_t hp_launch_bfv_decrypt_round(const HpLimb *limbs, const HpBfvConsts *bc, const HpBfvDecPlain &pc, u32 L, u32 n, u32 P, const u64 *x,
+                                       u64 *out, hipStream_t stream);
+// rows of any u64 words -> canonical residues: polynomial p, row k < R (modulus limbs[k]) from src + (p * src_ps + k) * n to
+// dst + (p * dst_ps + k) * n; src == dst with equal strides: in place
+hipError_t hp_launch_bfv_canonical(const HpLimb *limbs, u32 R, u32 n, u32 P, const u64 *src, u32 src_ps, u64 *dst, u32 dst_ps,
+                                   hipStream_t stream);
 // device samplers (hp_sample.hip; hp_sample.h has the stream layout).  One thread per ChaCha20 block of 8 words, at most
 // HP_SAMPLE_MAX_BLOCKS workgroups of 256 threads to a launch.
 // uniform: polynomial b < batch (id stream_id + b), row m < L (modulus rows.q[m], label rows.id[m]) -> out + b * stride + m * N, canonical

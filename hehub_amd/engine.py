@@ -593,6 +593,47 @@ class Engine:
                   self._ptr(ct1), self._ptr(ct2), self._ptr(key), self._ptr(out))
         return out
 
+    # -- BFV: moduli_qb = q_0..q_{L-1}, b_0..b_{M-1} (the auxiliary base), t = the plain modulus; canonical words out --------------------
+    def bfv_lift(self, moduli_qb, L: int, x, out=None):
+        """x [B][L][n] NTT form over Q -> [B][L+M][n]: the Q rows carried over, the B rows of the exact centred integer behind x"""
+        B, Lx, n = x.shape
+        assert Lx == L
+        E = len(moduli_qb)
+        out = self.empty((B, E, n)) if out is None else out
+        self._chk(self.lib.hp_dev_bfv_lift(self.h, n.bit_length() - 1, L, E - L, _u64arr(moduli_qb), B, self._ptr(x), self._ptr(out)))
+        return out
+
+    def bfv_scale_round(self, moduli_qb, L: int, t: int, x, out=None):
+        """x [B][L+M][n] NTT form over Q B -> [B][L][n]: floor((t x + h) / Q), h = (Q - 1) / 2, of every coefficient"""
+        B, E, n = x.shape
+        assert E == len(moduli_qb)
+        out = self.empty((B, L, n)) if out is None else out
+        self._chk(self.lib.hp_dev_bfv_scale_round(self.h, n.bit_length() - 1, L, E - L, _u64arr(moduli_qb), t, B, self._ptr(x), self._ptr(out)))
+        return out
+
+    def bfv_mult_low_level(self, moduli_qb, t: int, ct1, ct2, out=None):
+        """the scale-invariant product of BFV ciphertexts [B][2][L][n] -> the quadratic ciphertext [B][3][L][n]"""
+        B, _, L, n = ct1.shape
+        out = self.empty((B, 3, L, n)) if out is None else out
+        self._chk(self.lib.hp_dev_bfv_mult_low_level(self.h, n.bit_length() - 1, L, len(moduli_qb) - L, _u64arr(moduli_qb), t, B,
+                                                     self._ptr(ct1), self._ptr(ct2), self._ptr(out)))
+        return out
+
+    def bfv_mult_hks(self, moduli_ext, aux_moduli, t: int, k: int, alpha: int, ct1, ct2, key, out=None, key_L0=None):
+        """bfv_mult_low_level + relinearisation with a hybrid key (hks_keygen's for s_from = s * s, plain error rows) -> [B][2][L][n]"""
+        B, _, L, n = ct1.shape
+        out = self.empty((B, 2, L, n)) if out is None else out
+        self._hks("hp_dev_bfv_mult_relin_hks", key_L0, n.bit_length() - 1, L, k, alpha, _u64arr(moduli_ext), len(aux_moduli),
+                  _u64arr(aux_moduli), t, B, self._ptr(ct1), self._ptr(ct2), self._ptr(key), self._ptr(out))
+        return out
+
+    def bfv_decrypt_round(self, moduli, t: int, x, out=None):
+        """x [B][L][n] strict coefficient rows of c0 + c1 s (rlwe_decrypt_core's) -> the plaintext [B][n], words below t"""
+        B, L, n = x.shape
+        out = self.empty((B, n)) if out is None else out
+        self._chk(self.lib.hp_dev_bfv_decrypt_round(self.h, n, L, _u64arr(moduli), t, B, self._ptr(x), self._ptr(out)))
+        return out
+
     def poly_from_signed(self, moduli, coeffs):
         """small signed polynomials, coeffs [B][n] (any int64 values, device tensor) -> NTT form [B][L][n]: the words hp_dev_ntt produces
         from the strict residues.  How a ternary secret or an error polynomial gets to the device."""

@@ -849,6 +849,61 @@ int hp_dev_bgv_mult_relin_modswitch_hks(hp_ctx *ctx, size_t logn, size_t L, size
 int hp_dev_bgv_mult_relin_modswitch_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
                                            const uint64_t *moduli_ext, uint64_t plain_modulus, size_t batch, const uint64_t *d_ct1,
                                            const uint64_t *d_ct2, const uint64_t *d_key, uint64_t *d_out);
+/* BFV: the exact scale-invariant multiplication and the decryption rounding.  hehub names BFV first among its schemes and has no code
+ * for it; everything around BFV's multiplication is scheme-free and already here (hp_dev_mult_low_level over any moduli list, the
+ * hybrid switch with the CKKS ModDown -- BFV keys carry the error e, no factor t --, hp_dev_hks_keygen*, hp_dev_rlwe_encrypt_seeded,
+ * hp_dev_rlwe_decrypt_core).  What the calls below add is the pair of EXACT base conversions with the scaling between them.
+ *
+ * The convention (pinned by tests/bfv_model.py).  Q = q_0...q_{L-1} is the ciphertext modulus, odd, h = (Q - 1) / 2; B = b_0...b_{M-1}
+ * the auxiliary base; all L + M moduli distinct NTT primes of the ring degree; t the plain modulus, 2 <= t < every modulus.
+ * moduli_qb = q_0 .. q_{L-1}, b_0 .. b_{M-1}.  A BFV ciphertext (c0, c1) is u64[batch][2][L][N] in NTT form with
+ * c0 + c1 s = Delta m + e (mod Q), Delta = floor(Q / t).
+ *     centre_Q(x) = x  if x < floor(Q/2),  x - Q  otherwise     (the centring of ModDown and of hp_dev_rns_base_many_to_many)
+ *     lift        the integer centre_Q(x) behind the strict coefficient residues over Q, reduced into every b_j
+ *     scale       for a signed integer x given by its residues over Q B:  y = floor((t x + h) / Q), rounding to nearest (Q is odd:
+ *                 no ties).  v = t x + h residue-wise; r = [v]_Q in [0, Q), NOT centred, by mixed-radix composition over Q, reduced into
+ *                 every b_j; y = (v - r) Q^-1 mod b_j; then centre_B(y) reduced into every q_i
+ *     decryption  for x in [0, Q):  m = floor((t x + h) / Q) mod t = (h - r) Q^-1 mod t,  r = [t x + h]_Q reduced mod t  (t coprime to Q)
+ * Base size: the calls with a plain modulus require B >= 4 t N Q, decided exactly in multiword integers on the host.  Every tensor
+ * coefficient then has |x| <= N (Q + 1)^2 / 2, so t |x| + h < Q B / 2 and |y| < B / 2: both centrings are unambiguous.
+ * A plaintext is encrypted by hp_dev_rlwe_encrypt_seeded(error_scale = 1) on the coefficient rows (Delta mod q_i) * m, which the
+ * caller forms (for example with hp_dev_poly_scalar_mul); a relinearisation key is hp_dev_hks_keygen's for s_from = s * s and plain
+ * error rows; decryption is hp_dev_rlwe_decrypt_core followed by hp_dev_bfv_decrypt_round.
+ * Output contract of lift, scale_round, mult_low_level and decrypt_round: every word is the canonical residue (below q_m, below t),
+ * one reduction after the last transform, the same word at either parity level (the transforms inside are the level-B launches).
+ * mult_relin_hks[_at] have the contract of every hybrid call: on residues, words below 2 q_i, parity level A follows the context.
+ * Workspace, reserved up front (E = L + M): lift polys * L * N words; scale_round polys * (E + M) * N; mult_low_level
+ * batch * (10 E + 3 M) * N; mult_relin_hks that plus batch * 3 L * N plus the workspace of hp_dev_hks_switch.
+ * Refused with HP_EINVAL before anything is enqueued, the output untouched: a NULL context or pointer, a misaligned pointer;
+ * logn < 3 or > 16; L == 0, M == 0, polys or batch == 0; t < 2 or t >= any modulus; a modulus shared between Q and B, an even
+ * modulus; B < 4 t N Q; an output overlapping an input; everything hp_dev_hks_switch[_at] refuses, with its code.  HP_EUNSUPPORTED:
+ * L > 16, M > 16 or L + M > 32.  Chains that hp_dev_ntt refuses are refused with its code.
+ * Out of scope: a fused plaintext-scaling call; BFV rotations (the hoisted CKKS calls serve them: the ModDown is the same); a
+ * tensor-sum / dot form; modulus switching of BFV ciphertexts; the node, sharded and C++ host layers.
+ *
+ * hp_dev_bfv_lift: inverse transforms over Q, strict; the conversion; forward transforms over B.  The Q rows are carried over. */
+int hp_dev_bfv_lift(hp_ctx *ctx, size_t logn, size_t L, size_t M, const uint64_t *moduli_qb, size_t polys,
+                    const uint64_t *d_in /* u64[polys][L][N] NTT form, words < 2 * modulus */,
+                    uint64_t *d_out /* u64[polys][L+M][N] NTT form */);
+/* hp_dev_bfv_scale_round: inverse transforms over Q B, strict; the scaling; forward transforms over Q. */
+int hp_dev_bfv_scale_round(hp_ctx *ctx, size_t logn, size_t L, size_t M, const uint64_t *moduli_qb, uint64_t t, size_t polys,
+                           const uint64_t *d_in /* u64[polys][L+M][N] NTT form, words < 2 * modulus */,
+                           uint64_t *d_out /* u64[polys][L][N] NTT form */);
+/* hp_dev_bfv_mult_low_level: the lift of the four polynomials, hp_dev_mult_low_level's tensor product over L + M limbs into the
+ * workspace, hp_dev_bfv_scale_round of the three: word for word that composition. */
+int hp_dev_bfv_mult_low_level(hp_ctx *ctx, size_t logn, size_t L, size_t M, const uint64_t *moduli_qb, uint64_t t, size_t batch,
+                              const uint64_t *d_ct1, const uint64_t *d_ct2, uint64_t *d_quad /* u64[batch][3][L][N] */);
+/* hp_dev_bfv_mult_relin_hks: hp_dev_bfv_mult_low_level into the workspace, then hp_dev_hks_switch of y2 with (y0, y1) as its addend.
+ * moduli_ext = q_0 .. q_{L-1}, p_0 .. p_{k-1}; the auxiliary base may share primes with the special primes, none with Q. */
+int hp_dev_bfv_mult_relin_hks(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t M,
+                              const uint64_t *aux_moduli, uint64_t t, size_t batch, const uint64_t *d_ct1, const uint64_t *d_ct2,
+                              const uint64_t *d_key, uint64_t *d_out /* u64[batch][2][L][N] */);
+int hp_dev_bfv_mult_relin_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                                 size_t M, const uint64_t *aux_moduli, uint64_t t, size_t batch, const uint64_t *d_ct1,
+                                 const uint64_t *d_ct2, const uint64_t *d_key, uint64_t *d_out);
+/* hp_dev_bfv_decrypt_round: n = N (a power of two, 8 .. 65536); t only has to be coprime to Q. */
+int hp_dev_bfv_decrypt_round(hp_ctx *ctx, size_t n, size_t L, const uint64_t *moduli, uint64_t t, size_t polys,
+                             const uint64_t *d_x /* u64[polys][L][N] strict coefficient form */, uint64_t *d_m /* u64[polys][N], words < t */);
 /* ct u64[batch][2][L][N] -> out u64[batch][2][L-drops][N]; d_tmp: 2 * batch*2*(L-1)*N words (may be NULL for drops == 1) */
 int hp_dev_ckks_rescale_n(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, size_t drops, size_t batch,
                           const uint64_t *d_ct, uint64_t *d_tmp, uint64_t *d_out);
