@@ -155,6 +155,9 @@ SIGNATURES = {
     "hp_dev_ckks_mult_relin_rescale_hks_at": (INT, [P, szt, szt, szt, szt, szt, P, szt, P, P, P, P]),
     "hp_dev_ckks_relin_rescale_hks_at": (INT, [P, szt, szt, szt, szt, szt, P, szt, P, P, P]),
     "hp_dev_ckks_dot_relin_rescale_hks_at": (INT, [P, szt, szt, szt, szt, szt, P, szt, szt, P, P, P, P]),
+    # polynomial evaluation: linear combinations at the operands' own levels; a plan of hp_eval_step structs (EvalTerm/Form/Step below)
+    "hp_dev_ckks_lincomb": (INT, [P, szt, szt, P, szt, szt, P, P, P, P, P]),
+    "hp_dev_ckks_eval_plan_hks": (INT, [P, szt, szt, szt, szt, szt, P, szt, szt, P, szt, P, P, P]),
     "hp_dev_poly_from_signed": (INT, [P, szt, szt, P, szt, P, P]),
     "hp_dev_hks_keygen": (INT, [P, szt, szt, szt, szt, P, szt, P, P, P, P, P]),
     "hp_dev_hks_keygen_rot": (INT, [P, szt, szt, szt, szt, P, szt, P, P, P, P, P, P]),
@@ -197,6 +200,21 @@ SIGNATURES = {
     "hp_prof_end": (INT, [P, C.POINTER(szt), C.POINTER(C.c_double)]),
     "hp_prof_end_families": (INT, [P, szt, P, P, P, P]),
 }
+
+
+
+# the plan of hp_dev_ckks_eval_plan_hks: hp_eval_term / hp_eval_form / hp_eval_step of the header, field for field
+class EvalTerm(C.Structure):
+    _fields_ = [("elem", C.c_uint32), ("coef", C.POINTER(u64))]
+
+
+class EvalForm(C.Structure):
+    _fields_ = [("terms", C.c_uint32), ("term", C.POINTER(EvalTerm)), ("cst", C.POINTER(u64))]
+
+
+class EvalStep(C.Structure):
+    _fields_ = [("level", C.c_uint32), ("products", C.c_uint32), ("x", C.POINTER(EvalForm)), ("y", C.POINTER(EvalForm)), ("z", EvalForm)]
+
 
 _lib = None
 

@@ -737,6 +737,28 @@ extern "C" int hp_dev_ckks_relin_rescale_hks(hp_ctx *ctx, size_t logn, size_t L,
     return hp_dev_ckks_relin_rescale_hks_at(ctx, logn, L, L, k, alpha, moduli_ext, batch, d_quad, d_key, d_out);
 }
 
+// the same tail for a caller inside the engine that already holds the context lock (hp_api_eval.cpp: one per step of a plan)
+namespace hpi {
+int hks_limits(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t batch) {
+    return HksCall(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch, 0).rc;
+}
+int hks_relin_rescale_shape(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                            size_t batch, size_t *ws_words) {
+    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch, 0);
+    if (c.rc) return c.rc;
+    if (L < 2) return fail(ctx, HP_EINVAL, "Unable to drop the only one prime.");
+    if (c.open()) return c.rc;
+    *ws_words = relin_rescale_words(c, batch);
+    return HP_OK;
+}
+int hks_relin_rescale_step(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                           size_t batch, const u64 *quad, const u64 *key, u64 *out, Carver &cv) {
+    HksCall c(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch, 0);
+    if (c.rc || c.open()) return c.rc;
+    return relin_rescale(c, batch, quad, key, out, cv);
+}
+} // namespace hpi
+
 // ---- sums of products: lazy relinearisation ----------------------------------------------------------------------------------------
 // rescale(relin(sum_t a_t (x) b_t)) = rescale(sum_t (d0_t, d1_t) + switch(sum_t d2_t)), residue for residue: T products pay one switch
 // and one rounding.  The quadratic sum is one streaming kernel (k_tensor_sum, hp_ks.hip), one launch per argument table.

@@ -38,6 +38,28 @@ int chk(hp_ctx *ctx, hipError_t e, const char *what) {
     return HP_OK;
 }
 
+int stage_upload(hp_ctx *ctx, const void *host, size_t bytes, void *dptr) {
+    if (bytes == 0) return HP_OK;
+    if (!ctx->ev_stage) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_stage, hipEventDisableTiming));
+    else HIP_TRY(ctx, hipEventSynchronize(ctx->ev_stage));   // the previous copy out of the block (not the kernels after it)
+    if (bytes > ctx->stage_bytes) {
+        if (ctx->stage) HIP_TRY(ctx, hipHostFree(ctx->stage));
+        ctx->stage = nullptr;
+        ctx->stage_bytes = 0;
+        const size_t room = (bytes + 65535) & ~(size_t)65535;
+        hipError_t e = hipHostMalloc(&ctx->stage, room, hipHostMallocPortable);
+        if (e != hipSuccess) {
+            ctx->stage = nullptr;
+            return fail(ctx, HP_ENOMEM, std::string("staging hipHostMalloc: ") + hipGetErrorString(e));
+        }
+        ctx->stage_bytes = room;
+    }
+    memcpy(ctx->stage, host, bytes);
+    HIP_TRY(ctx, hipMemcpyAsync(dptr, ctx->stage, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_stage, ctx->stream));
+    return HP_OK;
+}
+
 int upload(hp_ctx *ctx, const void *host, size_t bytes, void **dptr) {
     HIP_TRY(ctx, hipMalloc(dptr, bytes));
     HIP_TRY(ctx, hipMemcpy(*dptr, host, bytes, hipMemcpyHostToDevice));
@@ -524,6 +546,8 @@ void hp_ctx_destroy(hp_ctx *ctx) {
         if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
         if (ctx->ev_switch) (void)hipEventDestroy(ctx->ev_switch);
         if (ctx->ev_tail) (void)hipEventDestroy(ctx->ev_tail);
+        if (ctx->ev_stage) (void)hipEventDestroy(ctx->ev_stage);
+        if (ctx->stage) (void)hipHostFree(ctx->stage);
         (void)hipStreamDestroy(ctx->own_stream);
     }
     delete ctx;

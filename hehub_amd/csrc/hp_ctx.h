@@ -4,6 +4,7 @@
 //   hp_api_poly.cpp    drop-in host entry points, device-resident polynomial batches, encrypt / decrypt cores, base conversions
 //   hp_api_scheme.cpp  key switch, drop-last-prime, relinearisation, rotations, the mult pipelines, limb-range stages
 //   hp_api_hks.cpp     hybrid key switch (extension)
+//   hp_api_eval.cpp    linear combinations of ciphertexts and the straight-line polynomial evaluator over the hybrid calls (extension)
 //   hp_api_bfv.cpp     BFV: exact lift / scale-and-round / multiplication over Q B, decryption rounding (extension)
 //   hp_drop.cpp        the constants of the fused drop launches (hp_drop.h: HpDropArgs field by field); host only, no HIP, no context
 //   hp_sample_host.cpp the device samplers' rules on the host (hp_sample.h: the ChaCha20 stream layout); host only, for the tests
@@ -112,6 +113,11 @@ struct hp_ctx {
     void *ws = nullptr;
     size_t ws_bytes = 0;
     unsigned long ws_generation = 0;   // bumped whenever the workspace is reallocated or released (captured graphs go stale)
+    // pinned staging block for small host tables a call uploads itself (stage_upload: the constants of hp_api_eval.cpp): grow-only;
+    // ev_stage marks the end of the last copy out of it, which the next use waits for before it overwrites the block
+    void *stage = nullptr;
+    size_t stage_bytes = 0;
+    hipEvent_t ev_stage = nullptr;
     // profiling
     std::string prof_family;
     bool prof_on = false;
@@ -200,6 +206,9 @@ int chk(hp_ctx *ctx, hipError_t e, const char *what);
 int fail_local(hp_ctx *ctx, int code, const std::string &msg);   // without the context lock: calling thread's slot only
 int chk_local(hp_ctx *ctx, hipError_t e, const char *what);
 int upload(hp_ctx *ctx, const void *host, size_t bytes, void **dptr);
+// host words -> device memory of the caller's (workspace), enqueued on the context's stream: the words travel through the context's
+// pinned staging block, so the caller's buffer is free when this returns and nothing depends on how the runtime treats pageable memory
+int stage_upload(hp_ctx *ctx, const void *host, size_t bytes, void *dptr);
 
 // ---- caches -----------------------------------------------------------------------------------------------
 int get_tables(hp_ctx *ctx, u64 q, size_t logn, DevTables &out);
@@ -288,6 +297,18 @@ int drop_last(hp_ctx *ctx, const Plan *plan, size_t logn, size_t L, size_t P2, b
               u64 *out, Carver &cv);
 // moved = the automorphism of ct [rows][n]: the involution (conj), or the cycle by `step`
 int move_rows(hp_ctx *ctx, size_t logn, size_t rows, bool conj, size_t step, const u64 *ct, u64 *moved);
+
+// ---- the tail of the hybrid multiplication (hp_api_hks.cpp) for the steps of hp_dev_ckks_eval_plan_hks (hp_api_eval.cpp) ----
+// Both take the arguments of hp_dev_ckks_relin_rescale_hks_at and run under the caller's context lock.
+// hks_limits: what every hybrid call refuses on (logn, L, key_L0, k, alpha, batch) alone, with its code; fetches nothing.
+// hks_relin_rescale_shape: what that call refuses on the shape alone, and then what fetching the level's plan and constants refuses (a chain that is not
+// pairwise coprime, a modulus without transforms), each with its code; *ws_words = the workspace relin_rescale carves.  Enqueues nothing.
+int hks_limits(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t batch);
+int hks_relin_rescale_shape(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                            size_t batch, size_t *ws_words);
+// that call's code on a shape the function above has passed: quad [batch][3][L][N] -> out [batch][2][L-1][N], workspace from cv
+int hks_relin_rescale_step(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *moduli_ext,
+                           size_t batch, const u64 *quad, const u64 *key, u64 *out, Carver &cv);
 
 // ---- BFV on an open shape (hp_api_bfv.cpp), also used by the relinearising calls of hp_api_hks.cpp ----
 struct BfvShape {

@@ -164,6 +164,16 @@ size_t tensor_sum_max_terms(const u64 *moduli, size_t L, size_t table_max) {
     return r < table_max ? (size_t)r : table_max;
 }
 
+size_t lincomb_max_terms(const u64 *moduli, size_t L, size_t table_max) {
+    typedef unsigned __int128 u128;
+    u64 q = 0;
+    for (size_t m = 0; m < L; m++) q = std::max(q, moduli[m]);
+    if (q < 2 || q >> 62) return 0;   // ((q - 1)(2q - 1) then stays below 2^125)
+    const u128 top = ((((u128)1 << 64) - q) << 64) - 1 - 3 * (u128)q;
+    const u128 r = top / (((u128)q - 1) * (2 * (u128)q - 1));
+    return r < table_max ? (size_t)r : table_max;
+}
+
 bool hks_bsgs_plan(const u64 *mext, size_t n, size_t L, size_t k, size_t alpha, size_t batch, size_t babies, size_t giants,
                    HksBsgsPlan &out) {
     out = HksBsgsPlan();

@@ -152,6 +152,12 @@ size_t hks_lintrans_max_rotations(const u64 *mext, size_t E, size_t nd, size_t t
 //   q == 0 or q >= 2^62: 0;  else min(table_max, floor(((2^64 - q) 2^64 - 1) / (2 (2q - 1)^2)))
 // -- the whole table of 32 for every modulus the transforms accept (below 2^59.5), 30 at q = 2^60.  Exact integers.
 size_t tensor_sum_max_terms(const u64 *moduli, size_t L, size_t table_max);
+// How many terms one launch of k_ct_lincomb (hp_lincomb.hip) may sum, at most table_max; 0: not even one.  With q the largest modulus
+// of the chain, operand words at most 2q - 1, coefficients at most q - 1, and the constant (below q) plus an accumulated word (below
+// 2q) on top, T terms sum to at most T (q - 1)(2q - 1) + 3q, which the same Montgomery step must find at most (2^64 - q) 2^64 - 1:
+//   q < 2 or q >= 2^62: 0;  else min(table_max, floor(((2^64 - q) 2^64 - 1 - 3q) / ((q - 1)(2q - 1))))
+// -- the whole table of 32 for every modulus below 2^60.9, 28 at q = 2^61 - 1, 6 just below 2^62.  Exact integers.
+size_t lincomb_max_terms(const u64 *moduli, size_t L, size_t table_max);
 // The pass plan and the workspace of hp_dev_ckks_lintrans_bsgs_hks (hp_api_hks.cpp), a function of the shape alone -- never of the
 // steps or of which diagonals are present.  With E = L + k, nd = ceil(L / alpha), pad(w) = w words rounded up to 256 bytes:
 //   baby_pass     babies per pre-sum launch (and per baby-stage launch): hks_lintrans_max_rotations(mext, E, nd, HP_BSGS_TABLE_MAX) --

@@ -142,6 +142,20 @@ struct HpTensorSumTable {
 };
 hipError_t hp_launch_tensor_sum(const HpLimb *limbs, u32 L, u32 n, u32 P, const HpTensorSumTable &tab, bool add_prev, u64 *quad,
                                 hipStream_t stream);
+// linear combination of ciphertexts (hp_lincomb.hip; hp_dev_ckks_lincomb, the linear forms of hp_dev_ckks_eval_plan_hks): term j = the
+// batch src[j], [P][2][limbs[j]][n] with limbs[j] >= L and words below 2 * modulus, read in its first L limb rows
+//   -> out [P][out_polys][L][n], polynomials 0 and 1 (out_polys = 2: a ciphertext batch; 3: the (d0, d1) of a quad):
+//      ([accumulate] out + sum_j coef[j][m] src[j] + (polynomial 0) coef[terms][m]) mod q_m, canonical (below q_m)
+// d_coef: DEVICE u64[terms + 1][L], residues below q_m (row `terms`: the constant).  terms <= hpi::lincomb_max_terms (hp_drop.h);
+// terms == 0: the constant (and the accumulated word) alone.  The addresses travel as kernel arguments.
+#define HP_LINCOMB_MAX 32
+struct HpLincombTable {
+    const u64 *src[HP_LINCOMB_MAX];
+    u32 limbs[HP_LINCOMB_MAX];
+    u32 terms;
+};
+hipError_t hp_launch_ct_lincomb(const HpLimb *limbs, u32 L, u32 n, u32 P, const HpLincombTable &tab, const u64 *d_coef, bool accumulate,
+                                u64 *out, u32 out_polys, hipStream_t stream);
 // rgsw.cpp:121-153: digits [P][L][L+1][n] (diagonal taken from pt [P][L][n]), key [L][2][L+1][n]
 //   -> out [P][2][L+1][n]
 // only output moduli [k_first, k_first + kc) of the L+1 are computed (kc = L+1: all)

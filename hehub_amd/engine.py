@@ -554,6 +554,37 @@ class Engine:
                   self._ptr(key), self._ptr(out))
         return out
 
+    def ckks_lincomb(self, moduli, cts, coefs=None, cst=None, out=None):
+        """sum_j coefs[j] * cts[j] + cst over the L = len(moduli) first limbs of ciphertext batches [B][2][L_j][n], L_j >= L (device
+        tensors anywhere; words below 2q) -> [B][2][L][n], canonical words, by one streaming kernel.  coefs[j]: the L residues of an
+        integer constant (None: 1); cst: L residues added to every position of polynomial 0 (None: 0)."""
+        T, L = len(cts), len(moduli)
+        B, _, _, n = cts[0].shape
+        assert T > 0 and all(t.shape[0] == B and t.shape[1] == 2 and t.shape[3] == n and t.is_contiguous() and t.element_size() == 8 for t in cts)
+        assert coefs is None or len(coefs) == T
+        out = self.empty((B, 2, L, n)) if out is None else out
+        cp = (capi.P * T)(*[t.data_ptr() for t in cts])
+        limbs = (C.c_size_t * T)(*[int(t.shape[2]) for t in cts])
+        keep = [None if coefs is None or c is None else _u64arr(c) for c in (coefs if coefs is not None else [None] * T)]
+        kp = None if coefs is None else (capi.P * T)(*[None if c is None else C.addressof(c) for c in keep])
+        self._chk(self.lib.hp_dev_ckks_lincomb(self.h, n.bit_length() - 1, L, _u64arr(moduli), B, T, cp, limbs, kp,
+                                               None if cst is None else _u64arr(cst), self._ptr(out)))
+        return out
+
+    def ckks_poly_eval_hks(self, moduli_ext, k: int, alpha: int, ct, key, plan, key_L0=None):
+        """a plan of hehub_amd.polyeval (build_plan: a polynomial in the power or the Chebyshev basis) evaluated on the ciphertext
+        batch ct [B][2][L][n] with ONE relinearisation key (hks_keygen's for s * s, generated for key_L0 >= L moduli; None: L)
+        -> [B][2][plan.out_limbs][n]"""
+        B, _, L, n = ct.shape
+        assert len(moduli_ext) == L + k and plan.in_limbs == L
+        steps, keep = plan.marshal()
+        out = self.empty((B, 2, plan.out_limbs, n))
+        self._chk(self.lib.hp_dev_ckks_eval_plan_hks(self.h, n.bit_length() - 1, L, L if key_L0 is None else int(key_L0), k, alpha,
+                                                     _u64arr(moduli_ext), B, len(plan.steps), steps, plan.final_drops, self._ptr(ct),
+                                                     self._ptr(key), self._ptr(out)))
+        del keep
+        return out
+
     # -- BGV over the hybrid key switch: t = the plain modulus; keys are hks_keygen's / hks_keygen_rot's for error rows t * e ----------
     def bgv_hks_switch(self, moduli_ext, t: int, k: int, alpha: int, pt, key, out=None, key_L0=None):
         """hks_switch with the plain-modulus ModDown: pt [B][L][n] -> [B][2][L][n], out0 + out1 s_to = pt s_from + t * (small)"""

@@ -649,6 +649,63 @@ int hp_dev_ckks_relin_rescale_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t 
 int hp_dev_ckks_dot_relin_rescale_hks_at(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
                                          const uint64_t *moduli_ext, size_t batch, size_t terms, const uint64_t *const *d_a,
                                          const uint64_t *const *d_b, const uint64_t *d_key, uint64_t *d_out);
+/* Polynomial evaluation: the non-linear half of a CKKS program (a sigmoid, GELU or comparison approximated by a polynomial, the
+ * EvalMod step of bootstrapping) over the hybrid key switch.  The engine is exact integer arithmetic and "scale" is the caller's
+ * notion, so -- as with keys and diagonals -- the caller supplies the constants: the NTT form of a constant is that constant in every
+ * position, so a plaintext constant is an integer given by its residues, and no encoder is involved.
+ *
+ * hp_dev_ckks_lincomb: d_out u64[batch][2][L][N] = sum_{j < terms} coef_j * ct_j + cst  (mod each q_m), every word CANONICAL (< q_m),
+ * the same at either parity level.  d_cts is a HOST array of device addresses (the convention of hp_dev_ckks_tensor_sum); ciphertext
+ * j is a batch u64[batch][2][ct_limbs[j]][N] with ct_limbs[j] >= L, read in its first L limb rows -- dropping limbs costs no copy.
+ * coefs is a HOST array of HOST pointers, coefs[j] = the L residues of coefficient j, each below q_m (coefs == NULL or coefs[j] ==
+ * NULL: 1); cst = L residues below q_m, added to every position of polynomial 0 only (NULL: 0).
+ * Every operand word MUST be below 2 * modulus (the precondition of hp_dev_ckks_tensor_sum, for its reason: a larger word can wrap the
+ * 128-bit sums unnoticed).  One streaming kernel, one launch per 32 terms (fewer from q = 2^61 on), one reduction per output word,
+ * 8 * (terms + 1) bytes of device memory traffic per output word; the workspace holds the coefficients, (terms + launches) * L words.
+ * HP_EINVAL before anything is enqueued: L == 0 or L > 32, batch == 0, terms == 0, a NULL array (coefs and cst excepted), a NULL or
+ * misaligned operand address, ct_limbs[j] < L or > 32, a coefficient or constant residue >= its modulus, d_out NULL, misaligned or
+ * overlapping an operand.  HP_EUNSUPPORTED: a modulus of 2^62 or more. */
+int hp_dev_ckks_lincomb(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, size_t batch, size_t terms,
+                        const uint64_t *const *d_cts /* HOST */, const size_t *ct_limbs /* each >= L */,
+                        const uint64_t *const *coefs /* HOST, entries u64[L] or NULL */, const uint64_t *cst, uint64_t *d_out);
+/* hp_dev_ckks_eval_plan_hks: a straight-line program of steps of ONE kind.  Element 0 is the input batch d_ct u64[batch][2][L][N];
+ * element s + 1 is the result of step s.  A linear form over earlier elements is F = sum_j coef_j * E_{elem_j} + cst, coef_j and cst
+ * HOST arrays of `level` residues below q_m (coef == NULL: 1, cst == NULL: 0; cst goes to polynomial 0 only).  Step s:
+ *     E_{s+1} = rescale_{q_{level-1}}( relin( sum_{t < products} X_t (x) Y_t ) + Z )               -> level - 1 limbs
+ * Every referenced element is read in its first `level` limb rows (its own limb count must be >= level: the mod-drop, no copy).
+ * products == 0: the step is rescale(Z) by hp_dev_ckks_rescale's code, no key switch.  This expresses a power B_a B_b, the Chebyshev
+ * recurrence rescale(relin(2 T_a (x) T_b) - kappa T_{a-b}), a leaf sum_j lambda_j B_j + c, the flat recombination
+ * sum_g leaf_g (x) G_g under ONE key switch, and the recursive form node = left (x) G + right.
+ * A step is, word for word and at either parity level (which follows the context), this composition of the calls above at
+ * moduli_ext = q_0..q_{level-1}, p_0..p_{k-1}: each X, Y form by hp_dev_ckks_lincomb into workspace (a form of one term with coef ==
+ * NULL, cst == NULL and an element of exactly `level` limbs is passed by address, no copy); the quadratic sum into a workspace quad
+ * -- products == 1: the tensor product of hp_dev_ckks_mult_relin_rescale_hks_at (with pass-through forms the step IS that call),
+ * more: hp_dev_ckks_tensor_sum --; Z added to the quad's (d0, d1) by the lincomb kernel; hp_dev_ckks_relin_rescale_hks_at on it.
+ * After the last step, final_drops rescales by hp_dev_ckks_rescale_n's code: d_out u64[batch][2][level_last - 1 - final_drops][N].
+ * d_relin_key: as the _at calls take it, generated for key_L0 >= L ciphertext moduli; one key serves every level.
+ * Every operand word of d_ct MUST be below 2 * modulus.
+ * Workspace, reserved once before anything is enqueued, a function of (N, k, alpha, batch, the plan's levels and counts), with
+ * pad = rounded up to 256 bytes and B = batch:
+ *     sum over the forms that are not passed by address of (terms + launches) * level words            the constants
+ *   + sum_s pad(B 2 (level_s - 1) N)                every element stays live (the last is d_out itself when final_drops == 0)
+ *   + 2 pad(B 2 (level_last - 2) N)                 only with final_drops >= 2
+ *   + the largest, over the steps, of  materialised forms * pad(B 2 level N) + pad(B 3 level N) + the workspace of
+ *     hp_dev_ckks_relin_rescale_hks_at at that level  (products == 0: pad(B 2 level N) + hp_dev_ckks_rescale's).
+ * HP_EINVAL before anything is enqueued, d_out untouched: a NULL or misaligned pointer, steps == 0 or > 64, level < 2, a level above
+ * a referenced element's limb count (or above L), a reference to an element not yet computed, an X or Y form with no term, a step
+ * with neither a product nor a term, a coefficient or constant residue >= its modulus, final_drops that leaves no limb, d_out
+ * overlapping d_ct; and everything the _at calls refuse at any of the plan's levels, with their code.  HP_EUNSUPPORTED: a modulus of
+ * 2^62 or more.
+ * Out of scope: a tree-mode (depth-optimal, recursive) plan builder; the node, sharded and C++ host layers; CKKS encoding; the
+ * odd/even polynomial optimisation; freeing dead elements. */
+typedef struct { uint32_t elem; const uint64_t *coef; } hp_eval_term;                 /* coef: HOST u64[level], NULL = 1 */
+typedef struct { uint32_t terms; const hp_eval_term *term; const uint64_t *cst; } hp_eval_form;
+typedef struct { uint32_t level, products; const hp_eval_form *x, *y; hp_eval_form z; } hp_eval_step;
+int hp_dev_ckks_eval_plan_hks(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha,
+                              const uint64_t *moduli_ext /* q_0..q_{L-1}, p_0..p_{k-1} */, size_t batch,
+                              size_t steps, const hp_eval_step *plan, size_t final_drops,
+                              const uint64_t *d_ct, const uint64_t *d_relin_key /* as the _at calls, for key_L0 */,
+                              uint64_t *d_out /* u64[batch][2][level_last - 1 - final_drops][N] */);
 /* Hybrid keys generated on the device.  In the three calls below the uniform rows a and the error polynomials e are INPUTS (the
  * seeded forms further down draw them on the device, hp_dev_sample_*), so
  * a call is deterministic and every output word is pinned by the exact model (tests/test_gpu_hks_keygen.py); what runs here is the
