@@ -20,7 +20,8 @@ SOURCES = ["hp_ctx.cpp", "hp_prof.cpp", "hp_api_poly.cpp", "hp_api_scheme.cpp", 
            "hp_tables.cpp", "hp_drop.cpp", "hp_wire.cpp", "hp_sample_host.cpp",
            "hp_elem.hip", "hp_ks.hip", "hp_edge.hip", "hp_hks.hip", "hp_bfv.hip", "hp_lincomb.hip",   # coefficient-wise kernels over hp_elem.h
            "hp_sample.hip",                                            # ChaCha20 samplers over hp_sample.h
-           "hp_ntt_generic.hip", "hp_ntt_split.hip", "hp_ntt_fast.hip", "hp_ntt_a.hip"]
+           "hp_ntt_generic.hip", "hp_ntt_split.hip", "hp_ntt_fast.hip", "hp_ntt_a.hip",
+           "hp_ntt_raise.hip"]                                         # ModRaise: its own instantiations over hp_ntt_tile.h
 # the FP64 residue kernels rely on separately rounded products (error-free transformations): no contraction of a * b + c
 EXTRA_FLAGS = {"hp_ntt_a.hip": ["-ffp-contract=off"]}
 ARCH = "gfx950"

@@ -158,6 +158,8 @@ SIGNATURES = {
     # polynomial evaluation: linear combinations at the operands' own levels; a plan of hp_eval_step structs (EvalTerm/Form/Step below)
     "hp_dev_ckks_lincomb": (INT, [P, szt, szt, P, szt, szt, P, P, P, P, P]),
     "hp_dev_ckks_eval_plan_hks": (INT, [P, szt, szt, szt, szt, szt, P, szt, szt, P, szt, P, P, P]),
+    # ModRaise: (logn, L, moduli, in_limbs, batch, d_ct, d_out)
+    "hp_dev_ckks_mod_raise": (INT, [P, szt, szt, P, szt, szt, P, P]),
     "hp_dev_poly_from_signed": (INT, [P, szt, szt, P, szt, P, P]),
     "hp_dev_hks_keygen": (INT, [P, szt, szt, szt, szt, P, szt, P, P, P, P, P]),
     "hp_dev_hks_keygen_rot": (INT, [P, szt, szt, szt, szt, P, szt, P, P, P, P, P, P]),

@@ -2,6 +2,7 @@
 // polynomial batches (transforms, RnsIntVec operators, gathers), the encrypt / decrypt cores and the RNS base conversions.
 #include "hp_ctx.h"
 
+#include <algorithm>
 #include <cstring>
 
 using namespace hpi;
@@ -372,6 +373,81 @@ int hp_dev_rns_base_from_single(hp_ctx *ctx, size_t n, uint64_t old_modulus, siz
     ProfScope ps(ctx, "elem");
     return chk(ctx, hp_launch_base_from_single(plan->d_limbs, old_modulus, (u32)L, (u32)n, (u32)batch, in, out, ctx->stream),
                "base_from_single");
+}
+
+// ModRaise: a ciphertext read at its limb row 0 -> the chain q_0 .. q_{L-1}.  One strict inverse transform of the 2 * batch rows
+// into workspace, then the L - 1 forward transforms of every polynomial as ONE launch whose loads centre and reduce the coefficient
+// row (hp_ntt_raise.hip); row 0 is a canonical copy.  Where that launch does not apply -- a ring degree without tiled kernels, a
+// launch the split-limb path takes, parity level A -- the three existing calls are composed on d_out itself: the lift of
+// hp_dev_rns_base_from_single, the forward transforms of rows 1 .. L - 1 in place, and every word made canonical.
+int hp_dev_ckks_mod_raise(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, size_t in_limbs, size_t batch, const uint64_t *d_ct,
+                          uint64_t *d_out) {
+    HP_ENTER(ctx);
+    HP_REQUIRE(ctx, moduli, d_ct, d_out);
+    HP_ALIGNED(ctx, d_ct, d_out);
+    if (!logn_ok(logn)) return fail(ctx, HP_EUNSUPPORTED, HP_LOGN_MSG);
+    if (L < 2 || L > HP_MAX_LIMBS) return fail(ctx, HP_EINVAL, "mod_raise: 2 .. 32 moduli");
+    if (in_limbs < 1 || in_limbs > HP_MAX_LIMBS) return fail(ctx, HP_EINVAL, "mod_raise: an input of 1 .. 32 limbs");
+    if (batch == 0) return fail(ctx, HP_EINVAL, "empty batch");
+    for (size_t a = 0; a < L; a++)
+        for (size_t b = 0; b < a; b++)
+            if (moduli[a] == moduli[b]) return fail(ctx, HP_EINVAL, "mod_raise: a repeated modulus");
+    const size_t n = (size_t)1 << logn, P2 = 2 * batch;
+    // rows of one launch stay u32 and its workgroups below 2^31 (512 words per workgroup at the least)
+    if (batch > ((size_t)1 << 28) / (std::max(L, in_limbs) * ((n + 511) / 512)))
+        return fail(ctx, HP_EUNSUPPORTED, "mod_raise: too many ciphertexts for one call");
+    const uintptr_t i0 = (uintptr_t)d_ct, o0 = (uintptr_t)d_out;
+    if (o0 < i0 + P2 * in_limbs * n * 8 && i0 < o0 + P2 * L * n * 8) return fail(ctx, HP_EINVAL, "mod_raise: the output overlaps the input");
+    // the lift adds q - (q_0 mod q) to a residue below q (fused launch: below 2q), or forms (floor(q_0 / q) + 1) q - q_0 + c, at
+    // most q_0 + q (hp_dev_rns_base_from_single): both fit 64 bits whenever q_0 + q < 2^64, so the transforms' own limit -- a
+    // modulus of at most 59 bits as hehub counts them, q < 2^59.5 (hp::check_ntt_modulus) -- is the binding one
+    for (size_t m = 0; m < L; m++) {
+        if (moduli[m] < 2) return fail(ctx, HP_EINVAL, "modulus must be >= 2");
+        if (hp::log_modulus(moduli[m]) > 59)
+            return fail(ctx, HP_EUNSUPPORTED, "mod_raise: every modulus must have at most 59 bits (the transforms' limit)");
+    }
+    const Plan *plan;
+    int rc = get_plan(ctx, logn, moduli, L, true, &plan);
+    if (rc) return rc;
+    LevelScope lv(ctx, plan);
+    if (lv.rc) return lv.rc;
+    if ((rc = ws_reserve(ctx, padded(P2 * n)))) return rc;
+    u64 *coef = (u64 *)ctx->ws;
+    const u64 q0 = moduli[0];
+    // c = strict(INTT_{q_0}(row 0 of every polynomial)): a one-limb batch whose rows are in_limbs apart (strict words are the same at both levels)
+    if ((rc = run_ntt(ctx, batch_job(plan, logn, 1, P2, d_ct, coef, in_limbs, 1, 1, 1)))) return rc;
+    HpNttJob fj = batch_job(plan, logn, L - 1, P2, coef, d_out + n, 1, L, 0, 0);
+    fj.limbs = plan->d_limbs + 1;
+    if (tiled_ok(ctx, logn) && !ctx->cur_a && !split_ok(ctx, logn, fj.W)) {
+        fj.src_kstride = 0;
+        fj.pair_moduli = (u32)std::min((size_t)ctx->drop_group, L - 1);
+        HpRaiseArgs ra;
+        memset(&ra, 0, sizeof(ra));
+        ra.half = q0 / 2;
+        for (size_t m = 1; m < L; m++) ra.r[m - 1] = q0 % moduli[m];
+        {
+            ProfScope ps(ctx, "ntt_raise");
+            if ((rc = chk(ctx, hp_launch_ntt_raise(fj, ra, ctx->stream), "ModRaise NTT"))) return rc;
+        }
+    } else {
+        {
+            ProfScope ps(ctx, "elem");
+            if ((rc = chk(ctx, hp_launch_base_from_single(plan->d_limbs, q0, (u32)L, (u32)n, (u32)P2, coef, d_out, ctx->stream), "base_from_single")))
+                return rc;
+        }
+        fj.src = d_out + n;
+        fj.src_pstride = (u32)L;
+        if (ctx->cur_a) fj.limbs_a = plan->d_limbs_a + 1;
+        if ((rc = run_ntt(ctx, fj))) return rc;
+        if (!ctx->cur_a) {   // (the level-A transform has written canonical residues)
+            ProfScope ps(ctx, "elem");
+            if ((rc = chk(ctx, hp_launch_bfv_canonical(plan->d_limbs + 1, (u32)(L - 1), (u32)n, (u32)P2, d_out + n, (u32)L, d_out + n, (u32)L, ctx->stream),
+                          "canonical rows")))
+                return rc;
+        }
+    }
+    ProfScope ps(ctx, "elem");
+    return chk(ctx, hp_launch_bfv_canonical(plan->d_limbs, 1, (u32)n, (u32)P2, d_ct, (u32)in_limbs, d_out, (u32)L, ctx->stream), "row 0");
 }
 
 int hp_dev_rns_base_to_single_small(hp_ctx *ctx, size_t n, size_t L, const uint64_t *old_moduli, uint64_t new_modulus,

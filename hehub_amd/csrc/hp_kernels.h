@@ -64,6 +64,15 @@ hipError_t hp_launch_ntt_fast(const HpNttJob &job, hipStream_t stream);
 hipError_t hp_launch_ntt_split(const HpNttJob &job, hipStream_t stream);
 // the same tiling with FP64 residue butterflies (job.limbs_a; HP_NTT_BATCH and HP_NTT_SPREAD; the inverse is always strict)
 hipError_t hp_launch_ntt_a(const HpNttJob &job, hipStream_t stream);
+// ModRaise (hp_ntt_raise.hip; hp_dev_ckks_mod_raise): the tiled forward transform whose loads centre a strict coefficient row modulo
+// q_0 and reduce it into the item's modulus -- v = strict(barrett_q(c)) (+ q - (q_0 mod q) when c >= half), the load side of the
+// fused drop without its epilogue.  job: HP_NTT_BATCH, forward, level B, logn in [11, 15], every limb reading its polynomial's one
+// row (src_kstride 0, pair_moduli as in the fused drop); limb k of the job is job.limbs[k].  Output words are below 2 * modulus.
+struct HpRaiseArgs {
+    u64 half;               // floor(q_0 / 2): a coefficient from here on is negative
+    u64 r[HP_MAX_LIMBS];    // q_0 mod (modulus of limb k of the job)
+};
+hipError_t hp_launch_ntt_raise(const HpNttJob &job, const HpRaiseArgs &ra, hipStream_t stream);
 
 // ---- coefficient-wise kernels on [rows][n], limb of a row = row % L ---------------
 enum HpBinOp : int { HP_ADD = 0, HP_SUB = 1, HP_MUL = 2 };

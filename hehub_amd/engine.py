@@ -855,6 +855,17 @@ class Engine:
                                                        self._ptr(out)))
         return out
 
+    def ckks_mod_raise(self, moduli, ct, out=None):
+        """ModRaise (include/hehub_amd.h: hp_dev_ckks_mod_raise): ct [B][2][L_in][n] in NTT form, read at its limb row 0 (words
+        below 2 q_0) -> [B][2][L][n] over moduli = q_0 .. q_{L-1}: row m >= 1 the transform modulo q_m of the centred coefficients
+        of row 0, row 0 its canonical copy; residues, every word below 2 q_m."""
+        B, two, Lin, n = ct.shape
+        assert two == 2
+        L = len(moduli)
+        out = self.empty((B, 2, L, n)) if out is None else out
+        self._chk(self.lib.hp_dev_ckks_mod_raise(self.h, n.bit_length() - 1, L, _u64arr(moduli), Lin, B, self._ptr(ct), self._ptr(out)))
+        return out
+
     def rns_base_to_single_small(self, old_moduli, new_modulus, x):
         """returns (out[B][n], not_small[B]); not_small != 0 marks polynomials that need the host CRT branch."""
         B, L, n = x.shape

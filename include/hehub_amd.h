@@ -706,6 +706,32 @@ int hp_dev_ckks_eval_plan_hks(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0,
                               size_t steps, const hp_eval_step *plan, size_t final_drops,
                               const uint64_t *d_ct, const uint64_t *d_relin_key /* as the _at calls, for key_L0 */,
                               uint64_t *d_out /* u64[batch][2][level_last - 1 - final_drops][N] */);
+/* hp_dev_ckks_mod_raise: the first step of bootstrapping -- a ciphertext that has reached its last limb q_0 is read as a ciphertext
+ * over the whole chain q_0 .. q_{L-1}.  d_ct is u64[batch][2][in_limbs][N] in NTT form, of which only limb row 0 is read (the
+ * mod-drop convention of hp_dev_ckks_lincomb: no copy); every word read MUST be below 2 q_0.  With c = INTT_{q_0}(row 0) taken
+ * strict in [0, q_0) and v_i = c_i where c_i < floor(q_0 / 2), c_i - q_0 from there on (the centring of
+ * hp_dev_rns_base_from_single), d_out u64[batch][2][L][N] holds, as RESIDUES like every hybrid call's output: row m >= 1 congruent
+ * to NTT_{q_m}(v mod q_m), row 0 congruent to the input's row 0 and canonical, every word below 2 q_m; for every modulus the
+ * residues equal those of hp_dev_intt (strict) on row 0, hp_dev_rns_base_from_single, hp_dev_ntt.  The raised ciphertext decrypts
+ * to m + q_0 I for a small integer polynomial I, which the rest of a bootstrap removes (hehub_amd/bootstrap.py).
+ * For N = 2^11 .. 2^15 at parity level B: one strict inverse transform of the 2 * batch rows into workspace, then ONE forward launch
+ * of 2 * batch * (L - 1) transforms whose loads centre and reduce the coefficient row -- the lifted block is never written: L + 4
+ * rows per polynomial cross device memory instead of the 3 L + 3 of the three calls -- and a canonical copy of row 0.  Other ring
+ * degrees, launches of few transforms (the split-limb path's) and parity level A compose the existing kernels on d_out; at level A
+ * every word is canonical where the chain has level-A transforms.
+ * Workspace: 2 * batch * N words, a function of (N, batch) alone, reserved before anything is enqueued.
+ * HP_EINVAL before anything is enqueued, d_out untouched: L < 2 or L > 32, in_limbs == 0 or > 32, batch == 0, a NULL or misaligned
+ * pointer, d_out overlapping d_ct, a repeated modulus, a modulus the transforms refuse (2N does not divide q - 1).
+ * HP_EUNSUPPORTED: a modulus of more than 59 bits as hehub counts them (q >= 2^59.5).  That is the transforms' own limit; the
+ * lift's arithmetic -- a residue below q plus q - (q_0 mod q), or (floor(q_0 / q) + 1) q - q_0 + c <= q_0 + q in the composed form --
+ * needs only q_0 + q < 2^64.
+ * The rest of a bootstrap -- CoeffToSlot, EvalMod, SlotToCoeff -- is a plan over the calls above (hp_dev_ckks_lintrans_bsgs_hks_at,
+ * hp_dev_ckks_rescale, hp_dev_ckks_conjugate_hks_at, hp_dev_ckks_lincomb, hp_dev_ckks_eval_plan_hks) built and run by
+ * hehub_amd/bootstrap.py, because scales are the caller's notion.  Out of scope: sparse packing / SubSum; a single C entry for the
+ * pipeline (a C caller chains the same calls); the node, sharded and C++ host layers; a device encoder; sparse-secret encapsulation;
+ * the arcsine correction; iterated bootstrapping; hoisting across factors. */
+int hp_dev_ckks_mod_raise(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli /* q_0..q_{L-1} */, size_t in_limbs, size_t batch,
+                          const uint64_t *d_ct /* u64[batch][2][in_limbs][N] */, uint64_t *d_out /* u64[batch][2][L][N] */);
 /* Hybrid keys generated on the device.  In the three calls below the uniform rows a and the error polynomials e are INPUTS (the
  * seeded forms further down draw them on the device, hp_dev_sample_*), so
  * a call is deterministic and every output word is pinned by the exact model (tests/test_gpu_hks_keygen.py); what runs here is the
