@@ -16,8 +16,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libhehub_amd.so")
-SOURCES = ["hp_ctx.cpp", "hp_prof.cpp", "hp_api_poly.cpp", "hp_api_scheme.cpp", "hp_api_hks.cpp", "hp_api_eval.cpp", "hp_api_bfv.cpp", "hp_node.cpp",
-           "hp_tables.cpp", "hp_drop.cpp", "hp_wire.cpp", "hp_sample_host.cpp",
+SOURCES = ["hp_ctx.cpp", "hp_prof.cpp", "hp_api_poly.cpp", "hp_api_scheme.cpp", "hp_api_hks.cpp", "hp_api_hks_mult.cpp", "hp_api_keys.cpp",
+           "hp_api_eval.cpp", "hp_api_bfv.cpp", "hp_node.cpp", "hp_tables.cpp", "hp_drop.cpp", "hp_wire.cpp", "hp_sample_host.cpp",
            "hp_elem.hip", "hp_ks.hip", "hp_edge.hip", "hp_hks.hip", "hp_bfv.hip", "hp_lincomb.hip",   # coefficient-wise kernels over hp_elem.h
            "hp_sample.hip",                                            # ChaCha20 samplers over hp_sample.h
            "hp_ntt_generic.hip", "hp_ntt_split.hip", "hp_ntt_fast.hip", "hp_ntt_a.hip",

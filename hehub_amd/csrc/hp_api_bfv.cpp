@@ -1,13 +1,12 @@
 // hp_api_bfv.cpp -- C ABI, part 4 (extension): BFV's scale-invariant multiplication and decryption rounding; kernels in hp_bfv.hip,
 // constants in hp_bfv.h.  Exact integer arithmetic throughout (both base conversions by mixed-radix composition), pinned by a
-// Python-integer model and by decryption (tests/bfv_model.py).  The relinearising calls live beside the hybrid key switch
-// (hp_api_hks.cpp) and use bfv_mult from here.
+// Python-integer model and by decryption (tests/bfv_model.py).  The relinearising calls live with the other multiplication tails of
+// the hybrid key switch (hp_api_hks_mult.cpp) and use bfv_mult from here.
 // Every transform in this file is the level-B launch at either parity level, and one reduction to the canonical residue follows the
 // last one: the words do not depend on the level (the contract of the seeded calls).
 #include "hp_ctx.h"
 
 #include <algorithm>
-#include <string>
 
 namespace hpi {
 
@@ -50,12 +49,6 @@ int bfv_open(hp_ctx *ctx, size_t logn, size_t L, size_t M, const uint64_t *q, co
         if (with_t) bfv_plain(s.qb.data(), L + M, t, s.plain);
         return (int)HP_OK;
     });
-}
-
-static int bfv_no_overlap(hp_ctx *ctx, const char *call, const void *in, size_t in_bytes, const void *out, size_t out_bytes) {
-    const uintptr_t c0 = (uintptr_t)in, o0 = (uintptr_t)out;
-    if (o0 < c0 + in_bytes && c0 < o0 + out_bytes) return fail(ctx, HP_EINVAL, std::string(call) + ": the output overlaps an input");
-    return HP_OK;
 }
 
 // lift of P polynomials: in [P][in_ps rows][N] (NTT form, words below 2q, L rows used) -> out [P][L + M][N], canonical residues:
@@ -138,7 +131,7 @@ int hp_dev_bfv_lift(hp_ctx *ctx, size_t logn, size_t L, size_t M, const uint64_t
     int rc = bfv_check(ctx, logn, L, M, moduli_qb, moduli_qb + L, false, 0, polys);
     if (rc) return rc;
     const size_t n = (size_t)1 << logn;
-    if ((rc = bfv_no_overlap(ctx, "bfv_lift", d_in, polys * L * n * 8, d_out, polys * (L + M) * n * 8))) return rc;
+    if (ranges_overlap(d_in, polys * L * n * 8, d_out, polys * (L + M) * n * 8)) return fail(ctx, HP_EINVAL, "bfv_lift: the output overlaps an input");
     BfvShape s;
     if ((rc = bfv_open(ctx, logn, L, M, moduli_qb, moduli_qb + L, false, 0, s)) || (rc = ws_reserve(ctx, bfv_lift_bytes(s, polys)))) return rc;
     Carver cv(ctx->ws);
@@ -153,7 +146,7 @@ int hp_dev_bfv_scale_round(hp_ctx *ctx, size_t logn, size_t L, size_t M, const u
     int rc = bfv_check(ctx, logn, L, M, moduli_qb, moduli_qb + L, true, t, polys);
     if (rc) return rc;
     const size_t n = (size_t)1 << logn;
-    if ((rc = bfv_no_overlap(ctx, "bfv_scale_round", d_in, polys * (L + M) * n * 8, d_out, polys * L * n * 8))) return rc;
+    if (ranges_overlap(d_in, polys * (L + M) * n * 8, d_out, polys * L * n * 8)) return fail(ctx, HP_EINVAL, "bfv_scale_round: the output overlaps an input");
     BfvShape s;
     if ((rc = bfv_open(ctx, logn, L, M, moduli_qb, moduli_qb + L, true, t, s)) || (rc = ws_reserve(ctx, bfv_scale_bytes(s, polys)))) return rc;
     Carver cv(ctx->ws);
@@ -168,9 +161,9 @@ int hp_dev_bfv_mult_low_level(hp_ctx *ctx, size_t logn, size_t L, size_t M, cons
     int rc = bfv_check(ctx, logn, L, M, moduli_qb, moduli_qb + L, true, t, batch);
     if (rc) return rc;
     const size_t n = (size_t)1 << logn;
-    if ((rc = bfv_no_overlap(ctx, "bfv_mult_low_level", d_ct1, batch * 2 * L * n * 8, d_quad, batch * 3 * L * n * 8)) ||
-        (rc = bfv_no_overlap(ctx, "bfv_mult_low_level", d_ct2, batch * 2 * L * n * 8, d_quad, batch * 3 * L * n * 8)))
-        return rc;
+    if (ranges_overlap(d_ct1, batch * 2 * L * n * 8, d_quad, batch * 3 * L * n * 8) ||
+        ranges_overlap(d_ct2, batch * 2 * L * n * 8, d_quad, batch * 3 * L * n * 8))
+        return fail(ctx, HP_EINVAL, "bfv_mult_low_level: the output overlaps an input");
     BfvShape s;
     if ((rc = bfv_open(ctx, logn, L, M, moduli_qb, moduli_qb + L, true, t, s)) || (rc = ws_reserve(ctx, bfv_mult_bytes(s, batch)))) return rc;
     Carver cv(ctx->ws);
@@ -194,10 +187,10 @@ int hp_dev_bfv_decrypt_round(hp_ctx *ctx, size_t n, size_t L, const uint64_t *mo
         if (!(moduli[i] & 1) || moduli[i] < 3) return fail(ctx, HP_EINVAL, "bfv: the moduli must be odd");
     HpBfvDecPlain pc;
     if (!bfv_dec_plain(moduli, L, t, pc)) return fail(ctx, HP_EINVAL, "bfv: the plain modulus must be coprime to the ciphertext modulus");
-    int rc = bfv_no_overlap(ctx, "bfv_decrypt_round", d_x, polys * L * n * 8, d_m, polys * n * 8);
-    if (rc) return rc;
+    if (ranges_overlap(d_x, polys * L * n * 8, d_m, polys * n * 8)) return fail(ctx, HP_EINVAL, "bfv_decrypt_round: the output overlaps an input");
     const Plan *plan;
     const HpBfvConsts *bc;
+    int rc;
     if ((rc = get_plan(ctx, 0, moduli, L, false, &plan)) || (rc = get_bfv_consts(ctx, moduli, L, 0, &bc))) return rc;
     ProfScope ps(ctx, "bfv_decrypt_round");
     return chk(ctx, hp_launch_bfv_decrypt_round(plan->d_limbs, bc, pc, (u32)L, (u32)n, (u32)polys, d_x, d_m, ctx->stream), "bfv_decrypt_round");

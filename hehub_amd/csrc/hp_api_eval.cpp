@@ -2,10 +2,10 @@
 // and the straight-line evaluator built over them and the hybrid calls -- the non-linear half of a CKKS program (a polynomial
 // approximation of a sigmoid, a comparison, EvalMod) as a sequence of steps of ONE kind,
 //     E_{s+1} = rescale( relin( sum_t X_t (x) Y_t ) + Z ),      X_t, Y_t, Z linear forms over earlier elements,
-// whose recombination sum_g leaf_g (x) G_g pays ONE key switch (lazy relinearisation: hp_api_hks.cpp).  The engine is exact integer
+// whose recombination sum_g leaf_g (x) G_g pays ONE key switch (lazy relinearisation: hp_api_hks_mult.cpp).  The engine is exact integer
 // arithmetic: which steps, which constants and what they mean as scales is the caller's business (hehub_amd/polyeval.py builds
 // plans for the power and the Chebyshev basis).
-#include "hp_ctx.h"
+#include "hp_hks_call.h"
 
 #include <algorithm>
 #include <cstring>
@@ -88,12 +88,11 @@ extern "C" int hp_dev_ckks_lincomb(hp_ctx *ctx, size_t logn, size_t L, const uin
     if (!batch_fits(batch, L, n)) return fail(ctx, HP_EUNSUPPORTED, "lincomb: too many ciphertexts for one call");
     return contained(ctx, [&] {
         Form f;
-        const uintptr_t o0 = (uintptr_t)d_out;
         for (size_t t = 0; t < terms; t++) {
             const uint64_t *p = d_cts[t];
             if (!p || ((uintptr_t)p & 15u)) return fail(ctx, HP_EINVAL, "lincomb: NULL or misaligned operand");
             if (ct_limbs[t] < L || ct_limbs[t] > HP_MAX_LIMBS) return fail(ctx, HP_EINVAL, "lincomb: an operand with fewer limbs than L (or more than 32)");
-            if (o0 < (uintptr_t)p + batch * 2 * ct_limbs[t] * n * 8 && (uintptr_t)p < o0 + out_bytes)
+            if (ranges_overlap(p, batch * 2 * ct_limbs[t] * n * 8, d_out, out_bytes))
                 return fail(ctx, HP_EINVAL, "lincomb: the output overlaps an operand");
             if (coefs && !residues_ok(coefs[t], moduli, L)) return fail(ctx, HP_EINVAL, "lincomb: a coefficient residue is not below its modulus");
             f.src.push_back(p);
@@ -152,7 +151,7 @@ extern "C" int hp_dev_ckks_eval_plan_hks(hp_ctx *ctx, size_t logn, size_t L, siz
     if (L < 1 || k < 1 || L + k > HP_MAX_LIMBS) return fail(ctx, HP_EINVAL, "unsupported number of moduli");
     if (batch == 0) return fail(ctx, HP_EINVAL, "empty batch");
     // what every hybrid call refuses on the shape alone, whether or not a step of the plan switches
-    if (int lim = hks_limits(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch)) return lim;
+    if (int lim = HksCall(ctx, logn, L, key_L0, k, alpha, moduli_ext, batch, 0).rc) return lim;
     if (steps == 0 || steps > 64) return fail(ctx, HP_EINVAL, "eval_plan: 1 .. 64 steps");
     const size_t n = (size_t)1 << logn;
     if (!batch_fits(batch, L, n)) return fail(ctx, HP_EUNSUPPORTED, "eval_plan: too many ciphertexts for one call");
@@ -200,8 +199,7 @@ extern "C" int hp_dev_ckks_eval_plan_hks(hp_ctx *ctx, size_t logn, size_t L, siz
         }
         if (final_drops >= limbs[steps]) return bad("the final drops leave no limb");
         const size_t out_limbs = limbs[steps] - final_drops;
-        const uintptr_t c0 = (uintptr_t)d_ct, o0 = (uintptr_t)d_out;
-        if (o0 < c0 + batch * 2 * L * n * 8 && c0 < o0 + batch * 2 * out_limbs * n * 8) return bad("the output overlaps the input");
+        if (ranges_overlap(d_ct, batch * 2 * L * n * 8, d_out, batch * 2 * out_limbs * n * 8)) return bad("the output overlaps the input");
         // the levels' own refusals (the _at calls', with their code), the range of the sums, and the sizes
         size_t coef_words = 0, scratch = 0, elem_words = 0;
         for (size_t s = 0; s < steps; s++) {
@@ -221,9 +219,11 @@ extern "C" int hp_dev_ckks_eval_plan_hks(hp_ctx *ctx, size_t logn, size_t L, siz
                     if (!pass_through(*f, lv)) mat++, coef_words += form_coef_words(f->terms(), e.pass_lin, lv);
             if (!e.z.empty()) coef_words += form_coef_words(e.z.terms(), e.pass_lin, lv);
             if (!e.x.empty()) {
-                size_t ws;
-                if ((rc = hks_relin_rescale_shape(ctx, logn, lv, key_L0, k, alpha, e.mext.data(), batch, &ws))) return rc;
-                need = mat * (padded(batch * 2 * lv * n) / 8) + padded(batch * 3 * lv * n) / 8 + ws;
+                HksCall c(ctx, logn, lv, key_L0, k, alpha, e.mext.data(), batch, 0);   // (scoped: its level ends with this block)
+                if (c.rc) return c.rc;
+                if (lv < 2) return fail(ctx, HP_EINVAL, "Unable to drop the only one prime.");
+                if (c.open()) return c.rc;
+                need = mat * (padded(batch * 2 * lv * n) / 8) + padded(batch * 3 * lv * n) / 8 + relin_rescale_words(c, batch);
             } else {
                 const Plan *p;
                 if ((rc = get_plan(ctx, logn, moduli_ext, lv, true, &p))) return rc;
@@ -307,20 +307,13 @@ extern "C" int hp_dev_ckks_eval_plan_hks(hp_ctx *ctx, size_t logn, size_t L, siz
                 ProfScope ps(ctx, "tensor");
                 if ((rc = chk(ctx, hp_launch_tensor(lp->d_limbs, (u32)lv, 0, (u32)lv, (u32)n, (u32)batch, a[0], b[0], quad, ctx->stream), "tensor")))
                     return rc;
-            } else {        // several: hp_dev_ckks_tensor_sum's launches
-                for (size_t t0 = 0; t0 < T; t0 += e.pass_ts) {
-                    HpTensorSumTable tab;
-                    memset(&tab, 0, sizeof(tab));
-                    tab.terms = (u32)std::min(e.pass_ts, T - t0);
-                    std::copy(a.begin() + t0, a.begin() + t0 + tab.terms, tab.a);
-                    std::copy(b.begin() + t0, b.begin() + t0 + tab.terms, tab.b);
-                    ProfScope ps(ctx, "tensor");
-                    if ((rc = chk(ctx, hp_launch_tensor_sum(lp->d_limbs, (u32)lv, (u32)n, (u32)batch, tab, t0 != 0, quad, ctx->stream), "tensor_sum")))
-                        return rc;
-                }
+            } else if ((rc = tensor_sum(ctx, lp->d_limbs, n, lv, batch, e.pass_ts, {T, a.data(), b.data()}, quad))) {   // several: hp_dev_ckks_tensor_sum's launches
+                return rc;
             }
             if (!e.z.empty() && (rc = form_launch(ctx, lp->d_limbs, lv, n, batch, e.pass_lin, e.z, dc, true, quad, 3))) return rc;
-            if ((rc = hks_relin_rescale_step(ctx, logn, lv, key_L0, k, alpha, e.mext.data(), batch, quad, d_relin_key, dst[s], cv))) return rc;
+            HksCall c(ctx, logn, lv, key_L0, k, alpha, e.mext.data(), batch, 0);   // one call, and with it one level, per step
+            if (c.rc || c.open()) return c.rc;
+            if ((rc = relin_rescale(c, batch, quad, d_relin_key, dst[s], cv))) return rc;
         }
         const u64 *src = elem[steps];
         for (size_t d = 0; d < final_drops; d++) {   // hp_dev_ckks_rescale_n's sequence

@@ -305,7 +305,7 @@ int hp_dev_poly_cycle(hp_ctx *ctx, size_t logn, size_t L, size_t batch, size_t s
     if (!logn_ok(logn)) return fail(ctx, HP_EUNSUPPORTED, HP_LOGN_MSG);
     if (batch == 0) return HP_OK;
     if (in == out) return fail(ctx, HP_EINVAL, "cycle cannot run in place");
-    if (step >= ((size_t)1 << 17)) return fail(ctx, HP_EINVAL, "rotation step out of range");
+    if (!rot_step_ok(step)) return fail(ctx, HP_EINVAL, "rotation step out of range");
     const size_t n = (size_t)1 << logn;
     const u32 *perm;
     int rc = get_cycle_perm(ctx, logn, step, &perm);
@@ -396,8 +396,7 @@ int hp_dev_ckks_mod_raise(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *mo
     // rows of one launch stay u32 and its workgroups below 2^31 (512 words per workgroup at the least)
     if (batch > ((size_t)1 << 28) / (std::max(L, in_limbs) * ((n + 511) / 512)))
         return fail(ctx, HP_EUNSUPPORTED, "mod_raise: too many ciphertexts for one call");
-    const uintptr_t i0 = (uintptr_t)d_ct, o0 = (uintptr_t)d_out;
-    if (o0 < i0 + P2 * in_limbs * n * 8 && i0 < o0 + P2 * L * n * 8) return fail(ctx, HP_EINVAL, "mod_raise: the output overlaps the input");
+    if (ranges_overlap(d_ct, P2 * in_limbs * n * 8, d_out, P2 * L * n * 8)) return fail(ctx, HP_EINVAL, "mod_raise: the output overlaps the input");
     // the lift adds q - (q_0 mod q) to a residue below q (fused launch: below 2q), or forms (floor(q_0 / q) + 1) q - q_0 + c, at
     // most q_0 + q (hp_dev_rns_base_from_single): both fit 64 bits whenever q_0 + q < 2^64, so the transforms' own limit -- a
     // modulus of at most 59 bits as hehub counts them, q < 2^59.5 (hp::check_ntt_modulus) -- is the binding one

@@ -435,13 +435,13 @@ static int dev_ckks_automorphism(hp_ctx *ctx, size_t logn, size_t L, size_t key_
             if (!many->polys[b] || ((uintptr_t)many->polys[b] & 15u)) return fail(ctx, HP_EINVAL, "rotate_many: NULL or misaligned polynomial");
         for (size_t b = 0; b < batch; b++) {
             if (!many->keys[b] || ((uintptr_t)many->keys[b] & 15u)) return fail(ctx, HP_EINVAL, "rotate_many: NULL or misaligned key");
-            if (!(many->conj_of && many->conj_of[b]) && many->steps[b] >= ((size_t)1 << 17)) return fail(ctx, HP_EINVAL, "rotation step out of range");
+            if (!(many->conj_of && many->conj_of[b]) && !rot_step_ok(many->steps[b])) return fail(ctx, HP_EINVAL, "rotation step out of range");
         }
     } else {
         HP_REQUIRE(ctx, key);
         HP_ALIGNED(ctx, key);
     }
-    if (!conj && step >= ((size_t)1 << 17)) return fail(ctx, HP_EINVAL, "rotation step out of range");
+    if (!conj && !rot_step_ok(step)) return fail(ctx, HP_EINVAL, "rotation step out of range");
     const Plan *plan;
     if ((rc = get_plan(ctx, logn, moduli_ext, L + 1, true, &plan))) return rc;
     LevelScope lvl(ctx, plan);   // this call at parity level A if the context asks for it and the chain allows

@@ -3,7 +3,9 @@
 //   hp_prof.cpp        in-library kernel timing (HIP events on the launch stream)
 //   hp_api_poly.cpp    drop-in host entry points, device-resident polynomial batches, encrypt / decrypt cores, base conversions
 //   hp_api_scheme.cpp  key switch, drop-last-prime, relinearisation, rotations, the mult pipelines, limb-range stages
-//   hp_api_hks.cpp     hybrid key switch (extension)
+//   hp_api_hks.cpp     hybrid key switch (extension): the call object of hp_hks_call.h, switch, rotations, the diagonal transforms
+//   hp_api_hks_mult.cpp  the multiplication tails over the hybrid switch: CKKS mult / relin / dot, the tensor sum, BGV, BFV
+//   hp_api_keys.cpp    hybrid key generation, the device samplers, seeded RLWE encryption
 //   hp_api_eval.cpp    linear combinations of ciphertexts and the straight-line polynomial evaluator over the hybrid calls (extension)
 //   hp_api_bfv.cpp     BFV: exact lift / scale-and-round / multiplication over Q B, decryption rounding (extension)
 //   hp_drop.cpp        the constants of the fused drop launches (hp_drop.h: HpDropArgs field by field); host only, no HIP, no context
@@ -182,6 +184,10 @@ inline bool any_misaligned(std::initializer_list<const void *> ptrs) {
 }
 #define HP_ALIGNED(ctx, ...) \
     if (hpi::any_misaligned({__VA_ARGS__})) return hpi::fail(ctx, HP_EINVAL, "device pointers must be 16-byte aligned")
+// the calls that write their output while they still read an input refuse [a, a + a_bytes) meeting [b, b + b_bytes)
+inline bool ranges_overlap(const void *a, size_t a_bytes, const void *b, size_t b_bytes) {
+    return (uintptr_t)b < (uintptr_t)a + a_bytes && (uintptr_t)a < (uintptr_t)b + b_bytes;
+}
 
 // every entry point runs with the context's device current and puts the caller's device back when it returns: an application
 // that drives several GPUs from one thread (or uses torch next to the engine) keeps allocating where it thinks it does
@@ -277,6 +283,7 @@ struct ProfScope {
 
 // ---- transforms -------------------------------------------------------------------------------------------
 inline bool logn_ok(size_t logn) { return logn >= 1 && logn <= 16; }   // (ntt.cpp:26-29 takes any degree with 2N | q - 1; the reference's bit reversal is 16 bits wide, permutation.h:41-55)
+inline bool rot_step_ok(size_t step) { return step < ((size_t)1 << 17); }   // else "rotation step out of range"
 inline bool tiled_ok(const hp_ctx *ctx, size_t logn) { return !ctx->force_generic && logn >= 11 && logn <= 15; }
 inline bool fused_drop_ok(const hp_ctx *ctx, size_t logn) { return tiled_ok(ctx, logn) && !ctx->no_fused_drop; }
 // a launch of `items` limb transforms small enough for the split (latency) path
@@ -298,19 +305,7 @@ int drop_last(hp_ctx *ctx, const Plan *plan, size_t logn, size_t L, size_t P2, b
 // moved = the automorphism of ct [rows][n]: the involution (conj), or the cycle by `step`
 int move_rows(hp_ctx *ctx, size_t logn, size_t rows, bool conj, size_t step, const u64 *ct, u64 *moved);
 
-// ---- the tail of the hybrid multiplication (hp_api_hks.cpp) for the steps of hp_dev_ckks_eval_plan_hks (hp_api_eval.cpp) ----
-// Both take the arguments of hp_dev_ckks_relin_rescale_hks_at and run under the caller's context lock.
-// hks_limits: what every hybrid call refuses on (logn, L, key_L0, k, alpha, batch) alone, with its code; fetches nothing.
-// hks_relin_rescale_shape: what that call refuses on the shape alone, and then what fetching the level's plan and constants refuses (a chain that is not
-// pairwise coprime, a modulus without transforms), each with its code; *ws_words = the workspace relin_rescale carves.  Enqueues nothing.
-int hks_limits(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t batch);
-int hks_relin_rescale_shape(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *moduli_ext,
-                            size_t batch, size_t *ws_words);
-// that call's code on a shape the function above has passed: quad [batch][3][L][N] -> out [batch][2][L-1][N], workspace from cv
-int hks_relin_rescale_step(hp_ctx *ctx, size_t logn, size_t L, size_t key_L0, size_t k, size_t alpha, const uint64_t *moduli_ext,
-                           size_t batch, const u64 *quad, const u64 *key, u64 *out, Carver &cv);
-
-// ---- BFV on an open shape (hp_api_bfv.cpp), also used by the relinearising calls of hp_api_hks.cpp ----
+// ---- BFV on an open shape (hp_api_bfv.cpp), also used by the relinearising calls of hp_api_hks_mult.cpp ----
 struct BfvShape {
     size_t logn = 0, L = 0, M = 0, n = 0;
     std::vector<u64> qb;   // q_0 .. q_{L-1}, b_0 .. b_{M-1}
