@@ -55,6 +55,8 @@ SIGNATURES = {
     "hp_ctx_set_force_generic": (INT, [P, INT]),
     "hp_ctx_set_parity_level": (INT, [P, INT]),
     "hp_ctx_get_parity_level": (INT, [P]),
+    "hp_ctx_set_error_sampler": (INT, [P, C.c_uint32]),
+    "hp_ctx_get_error_sampler": (INT, [P]),
     "hp_ntt_negacyclic_inplace_lazy": (INT, [P, szt, u64, P]),
     "hp_intt_negacyclic_inplace_lazy": (INT, [P, szt, u64, P]),
     "hp_cache_ntt_factors_strict": (INT, [P, szt, P, szt]),
@@ -167,6 +169,7 @@ SIGNATURES = {
     "hp_dev_sample_uniform": (INT, [P, szt, szt, P, P, szt, P, u64, szt, P]),
     "hp_dev_sample_ternary": (INT, [P, szt, szt, P, u64, P]),
     "hp_dev_sample_cbd": (INT, [P, szt, szt, P, u64, P]),
+    "hp_dev_sample_gauss": (INT, [P, szt, szt, P, u64, P]),
     "hp_dev_hks_keygen_seeded": (INT, [P, szt, szt, szt, szt, P, szt, P, P, P, u64, u64, P]),
     "hp_dev_hks_keygen_rot_seeded": (INT, [P, szt, szt, szt, szt, P, szt, P, P, P, P, u64, u64, P]),
     "hp_dev_hks_key_expand": (INT, [P, szt, szt, szt, szt, P, szt, P, u64, P]),

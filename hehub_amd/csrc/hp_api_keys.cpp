@@ -172,6 +172,11 @@ extern "C" int hp_dev_sample_ternary(hp_ctx *ctx, size_t logn, size_t batch, con
 extern "C" int hp_dev_sample_cbd(hp_ctx *ctx, size_t logn, size_t batch, const uint8_t *seed, uint64_t stream, int64_t *d_out) {
     return dev_sample_signed(ctx, HP_SAMPLE_CBD, "sample_cbd", logn, batch, seed, stream, d_out);
 }
+extern "C" int hp_dev_sample_gauss(hp_ctx *ctx, size_t logn, size_t batch, const uint8_t *seed, uint64_t stream, int64_t *d_out) {
+    return dev_sample_signed(ctx, HP_SAMPLE_GAUSS, "sample_gauss", logn, batch, seed, stream, d_out);
+}
+// the profile scope of an error row drawn with the context's sampler (hp_ctx_set_error_sampler)
+static const char *error_scope(const hp_ctx *ctx) { return ctx->error_sampler == HP_SAMPLE_GAUSS ? "sample_gauss" : "sample_cbd"; }
 
 // the a rows of a key set from the seed: key r, digit d has the polynomial id stream + r * dnum + d and the limb ids 0 .. E-1.
 // mont: times 2^64 mod q_m, the finished [1] halves (hp_dev_hks_key_expand); else plain, for the generator to convert in place
@@ -193,7 +198,7 @@ static int seeded_ok(hp_ctx *ctx, size_t logn, size_t keys, const uint8_t *seed,
     if (error_scale == 0 || error_scale >= HP_SAMPLE_MAX_SCALE) return fail(ctx, HP_EINVAL, "error_scale must be positive and below 2^58");
     return HP_OK;
 }
-// the draw of a seeded generator: a into the [1] halves, error_scale * e into workspace (i64[keys][dnum][N]: a function of
+// the draw of a seeded generator: a into the [1] halves, error_scale * e (the context's error sampler) into workspace (i64[keys][dnum][N]: a function of
 // (N, dnum, keys) alone)
 struct KeygenSeededDraw {
     size_t keys;
@@ -207,9 +212,9 @@ struct KeygenSeededDraw {
         long long *e = (long long *)cv.take(keys * c.nd * c.n);
         if ((rc = sample_key_rows(c, keys, seed, stream, false, d_keys))) return rc;
         d_e = (const int64_t *)e;
-        ProfScope ps(c.ctx, "sample_cbd");
-        return chk(c.ctx, hp_launch_sample_signed(HP_SAMPLE_CBD, hp_sample_seed(seed), (u32)c.logn, keys * c.nd, stream, (long long)error_scale, e,
-                                                  c.ctx->stream), "sample_cbd");
+        ProfScope ps(c.ctx, error_scope(c.ctx));
+        return chk(c.ctx, hp_launch_sample_signed(c.ctx->error_sampler, hp_sample_seed(seed), (u32)c.logn, keys * c.nd, stream,
+                                                  (long long)error_scale, e, c.ctx->stream), error_scope(c.ctx));
     }
 };
 
@@ -254,9 +259,9 @@ extern "C" int hp_dev_hks_key_expand(hp_ctx *ctx, size_t logn, size_t L, size_t 
 }
 
 // ---- fresh ciphertexts from a seed (kernels in hp_sample.hip) ---------------------------------------------------------------------------
-// The small polynomials (errors, the public-key form's u) go from the keystream straight to the residues of every modulus
-// (k_sample_spread) and through the batched forward transform where the ciphertext will lie; one fused kernel then finishes the
-// rows.  The transforms are the level-B launches at either parity level and the last kernel reduces to the canonical residue, so
+// The small polynomials (errors by the context's error sampler, the public-key form's ternary u) go from the keystream straight to
+// the residues of every modulus (k_sample_spread) and through the batched forward transform where the ciphertext will lie; one
+// fused kernel then finishes the rows.  The transforms are the level-B launches at either parity level and the last kernel reduces to the canonical residue, so
 // the words do not depend on the level.
 static const char *ENC_SCALE_MSG = "the scale must be positive and below 2^58";
 
@@ -330,7 +335,7 @@ extern "C" int hp_dev_rlwe_encrypt_seeded(hp_ctx *ctx, size_t logn, size_t L, co
         ptn = Carver(ctx->ws).take(batch * L * n);
         pt_rows = L;
     }
-    if ((rc = small_ntt_rows(ctx, plan, rows, HP_SAMPLE_CBD, logn, L, batch, seed, stream, 1, error_scale, ct_rows, d_ct))) return rc;
+    if ((rc = small_ntt_rows(ctx, plan, rows, ctx->error_sampler, logn, L, batch, seed, stream, 1, error_scale, ct_rows, d_ct))) return rc;
     if (d_pt && (rc = run_ntt(ctx, batch_job(plan, logn, L, batch, d_pt, ptn, L, pt_rows, 0, 0)))) return rc;
     ProfScope ps(ctx, "enc_seeded");
     return chk(ctx, hp_launch_enc_seeded(hp_sample_seed(seed), rows, plan->d_limbs, (u32)L, (u32)logn, batch, stream, d_sk, ptn, pt_rows * n,
@@ -355,7 +360,7 @@ extern "C" int hp_dev_rlwe_encrypt_pk_seeded(hp_ctx *ctx, size_t logn, size_t L,
     Carver cv(ctx->ws);
     u64 *u = cv.take(batch * L * n), *ptn = d_pt ? cv.take(batch * L * n) : nullptr;
     // e0_b, e1_b: the ids stream + 2b, stream + 2b + 1 -- the 2 * batch polynomials of d_ct in order; u_b: the ternary sample of stream + 2b
-    if ((rc = small_ntt_rows(ctx, plan, rows, HP_SAMPLE_CBD, logn, L, 2 * batch, seed, stream, 1, error_scale, L, d_ct)) ||
+    if ((rc = small_ntt_rows(ctx, plan, rows, ctx->error_sampler, logn, L, 2 * batch, seed, stream, 1, error_scale, L, d_ct)) ||
         (rc = small_ntt_rows(ctx, plan, rows, HP_SAMPLE_TERNARY, logn, L, batch, seed, stream, 2, 1, L, u)))
         return rc;
     if (d_pt && (rc = run_ntt(ctx, batch_job(plan, logn, L, batch, d_pt, ptn, L, L, 0, 0)))) return rc;

@@ -462,7 +462,7 @@ int hp_ctx_fork(hp_ctx *parent, hp_ctx **out) {
     const int rc = make_ctx(parent->device, parent->sh, &c);
     if (rc) return fail(parent, rc, "hp_ctx_fork: could not create the lane's stream");
     parent->sh->refs++;
-    c->force_generic = parent->force_generic; c->parity_level = parent->parity_level;
+    c->force_generic = parent->force_generic; c->parity_level = parent->parity_level; c->error_sampler = parent->error_sampler;
     c->drop_group = parent->drop_group; c->spread_group = parent->spread_group; c->hks_two_step = parent->hks_two_step;
     c->hks_combine_kernel = parent->hks_combine_kernel; c->no_fused_drop = parent->no_fused_drop; c->no_pack48 = parent->no_pack48;
     c->no_pack40 = parent->no_pack40; c->no_double_drop = parent->no_double_drop; c->pack48_min_logn = parent->pack48_min_logn;
@@ -507,6 +507,15 @@ int hp_ctx_set_parity_level(hp_ctx *ctx, int level) {
     return HP_OK;
 }
 int hp_ctx_get_parity_level(hp_ctx *ctx) { return ctx ? ctx->parity_level : HP_EINVAL; }
+
+// the error distribution of the seeded key and ciphertext calls: a sampler kind of hp_sample.h
+int hp_ctx_set_error_sampler(hp_ctx *ctx, uint32_t kind) {
+    HP_ENTER(ctx);
+    if (kind != HP_SAMPLE_CBD && kind != HP_SAMPLE_GAUSS) return fail(ctx, HP_EINVAL, "error sampler: kind is 3 (centred binomial) or 4 (discrete Gaussian)");
+    ctx->error_sampler = kind;
+    return HP_OK;
+}
+int hp_ctx_get_error_sampler(hp_ctx *ctx) { return ctx ? (int)ctx->error_sampler : HP_EINVAL; }
 
 void hp_ctx_destroy(hp_ctx *ctx) {
     if (!ctx) return;

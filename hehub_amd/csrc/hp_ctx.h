@@ -101,6 +101,9 @@ struct hp_ctx {
     // parity level of the scheme-level pipelines (hp_ctx_set_parity_level; HP_PARITY_LEVEL=A): 0 = B, raw words identical to
     // hehub's (default); 1 = A, canonical residues through the FP64 transforms of hp_ntt_a.hip where the chain allows
     int parity_level = 0;
+    // the error distribution of the seeded calls (hp_ctx_set_error_sampler): a kind tag of hp_sample.h, 3 = centred binomial (default),
+    // 4 = discrete Gaussian
+    u32 error_sampler = HP_SAMPLE_CBD;
     bool cur_a = false;           // set for the duration of one entry point (under the context lock): this call runs at level A
     bool a_pending = false;       // a level-A call has been enqueued on THIS context since its last range_check
     unsigned long trips_seen = 0; // the family's range_trips when a_pending was set / last reported

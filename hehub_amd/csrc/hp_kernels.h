@@ -357,11 +357,11 @@ struct HpSampleRows {
 };
 hipError_t hp_launch_sample_uniform(const HpSampleSeed &seed, const HpSampleRows &rows, const HpLimb *mont_limbs, u32 L, u32 logn, u64 batch,
                                     u64 stream_id, u64 stride, u64 *out, hipStream_t stream);
-// kind HP_SAMPLE_TERNARY / HP_SAMPLE_CBD: out [batch][N] = scale * the sample of id stream_id + b
+// kind HP_SAMPLE_TERNARY / HP_SAMPLE_CBD / HP_SAMPLE_GAUSS: out [batch][N] = scale * the sample of id stream_id + b
 hipError_t hp_launch_sample_signed(u32 kind, const HpSampleSeed &seed, u32 logn, u64 batch, u64 stream_id, long long scale, long long *out,
                                    hipStream_t stream);
-// fresh ciphertexts.  spread: kind HP_SAMPLE_TERNARY / HP_SAMPLE_CBD; polynomial p < batch (id stream_id + p * id_step), row m < L ->
-// out + p * pstride + m * N = the canonical residues of scale * the sample modulo rows.q[m], coefficient form (rows.id is not read)
+// fresh ciphertexts.  spread: kind HP_SAMPLE_TERNARY / HP_SAMPLE_CBD / HP_SAMPLE_GAUSS; polynomial p < batch (id stream_id + p * id_step),
+// row m < L -> out + p * pstride + m * N = the canonical residues of scale * the sample modulo rows.q[m], coefficient form (rows.id is not read)
 hipError_t hp_launch_sample_spread(u32 kind, const HpSampleSeed &seed, const HpSampleRows &rows, u32 L, u32 logn, u64 batch, u64 stream_id,
                                    u64 id_step, long long scale, u64 pstride, u64 *out, hipStream_t stream);
 // ciphertext b < batch at ct + b * (with_c1 ? 2 : 1) * L * N, its c0 rows holding NTT(e_b) on entry (lazy transform words):

@@ -14,15 +14,16 @@
 #pragma once
 #include <cstddef>
 #include <cstdint>
+#include <utility>
 
 typedef uint64_t u64;
 typedef uint32_t u32;
 
-// the kind tag of word 13: the three samplers never share keystream under one (seed, stream)
-constexpr u32 HP_SAMPLE_UNIFORM = 1, HP_SAMPLE_TERNARY = 2, HP_SAMPLE_CBD = 3;
+// the kind tag of word 13: the four samplers never share keystream under one (seed, stream)
+constexpr u32 HP_SAMPLE_UNIFORM = 1, HP_SAMPLE_TERNARY = 2, HP_SAMPLE_CBD = 3, HP_SAMPLE_GAUSS = 4;
 constexpr u32 HP_SAMPLE_ATTEMPTS = 64;                 // candidates a uniform word may use up: attempts 0 .. 63
 constexpr u32 HP_SAMPLE_ETA = 21;                      // centred binomial: popcount of 21 bits minus popcount of the next 21
-constexpr u64 HP_SAMPLE_MAX_SCALE = (u64)1 << 58;      // error_scale below this: 21 * scale fits an int64_t
+constexpr u64 HP_SAMPLE_MAX_SCALE = (u64)1 << 58;      // error_scale below this: 21 * scale (binomial), 30 * scale (Gaussian) fit an int64_t
 constexpr u32 HP_SAMPLE_MAX_LIMB_ID = 256;
 
 struct HpSampleSeed {
@@ -112,10 +113,34 @@ constexpr int64_t hp_sample_cbd_word(u64 v) {
     return (int64_t)__builtin_popcountll(v & m) - (int64_t)__builtin_popcountll(v >> HP_SAMPLE_ETA & m);
 }
 
+// ---- discrete Gaussian, sigma = 16/5: range +-30, variance 10.24 ------------------------------------------------------------------------------
+// rho(k) = exp(-25 k^2 / 512), S = the sum of rho over all integers; the magnitude m has P(0) = rho(0) / S, P(m) = 2 rho(m) / S.
+// HP_SAMPLE_GAUSS_CDT[m] = floor(2^63 * (P(0) + .. + P(m))), m = 0 .. 29: entry 29 is 2^63 - 1 and every further one would be too.
+// (tests/gauss_model.py recomputes the literals in decimal arithmetic.)  The candidate's bit 0 is the sign, u = its other 63 bits,
+// m = the number of entries u has reached: statistical distance to D_{Z,3.2} below 2^-57.  All 30 compares, whatever the value:
+// nothing to diverge on.  The count is a fold over the index pack, unrolled by the language and not by an optimiser's choice: every
+// entry is a literal of its compare instruction -- no table in memory.
+constexpr u32 HP_SAMPLE_GAUSS_ENTRIES = 30;
+constexpr u64 HP_SAMPLE_GAUSS_CDT[HP_SAMPLE_GAUSS_ENTRIES] = {
+    1149872835429266008ull, 3340023666152832877ull, 5231742854224525755ull, 6713673034491318533ull, 7766573326200196558ull,
+    8445050402542556633ull, 8841576285654612683ull, 9051758678878186096ull, 9152802451769415979ull, 9196859074767746705ull,
+    9214281206174004120ull, 9220529764022708440ull, 9222562339745873205ull, 9223161995634596963ull, 9223322447917711088ull,
+    9223361386320111732ull, 9223369956674611011ull, 9223371667508612690ull, 9223371977254386295ull, 9223372028116140532ull,
+    9223372035690845298ull, 9223372036713969870ull, 9223372036839307001ull, 9223372036853232777ull, 9223372036854636067ull,
+    9223372036854764319ull, 9223372036854774950ull, 9223372036854775749ull, 9223372036854775804ull, 9223372036854775807ull};
+template <u32... I> constexpr u32 hp_sample_gauss_count(u64 u, std::integer_sequence<u32, I...>) {
+    return (0u + ... + (u32)(u >= HP_SAMPLE_GAUSS_CDT[I]));
+}
+constexpr int64_t hp_sample_gauss_word(u64 v) {
+    const u32 m = hp_sample_gauss_count(v >> 1, std::make_integer_sequence<u32, HP_SAMPLE_GAUSS_ENTRIES>{});
+    const u32 s = (u32)v & 1u;   // the conditional negation on the 32-bit count: (m ^ -s) + s
+    return (int64_t)(int32_t)((m ^ (0u - s)) + s);
+}
+
 // ---- a scaled small coefficient as the canonical residue modulo q (k_sample_spread, hp_dev_sample_small_ntt) ---------------------------------
-// v = scale * (a ternary or binomial word), |v| <= 21 * scale < 2^63: the magnitude modulo q, then the conditional negation q - r,
-// where r = 0 stays 0 (hp_dev_poly_from_signed's rule).  The magnitude is below q whenever 21 * scale < q -- the usual case, no
-// division; either way the same word.
+// v = scale * (a ternary, binomial or Gaussian word), |v| <= 30 * scale < 2^63: the magnitude modulo q, then the conditional negation
+// q - r, where r = 0 stays 0 (hp_dev_poly_from_signed's rule).  The magnitude is below q whenever 30 * scale < q -- the usual case,
+// no division; either way the same word.
 constexpr u64 hp_sample_residue(int64_t v, u64 q) {
     const bool neg = v < 0;
     const u64 a = neg ? (u64)0 - (u64)v : (u64)v;
@@ -123,12 +148,14 @@ constexpr u64 hp_sample_residue(int64_t v, u64 q) {
     return (neg && r) ? q - r : r;
 }
 constexpr int64_t hp_sample_small_word(u32 kind, u64 candidate) {
-    return kind == HP_SAMPLE_TERNARY ? hp_sample_ternary_word(candidate) : hp_sample_cbd_word(candidate);
+    return kind == HP_SAMPLE_TERNARY ? hp_sample_ternary_word(candidate)
+           : kind == HP_SAMPLE_GAUSS ? hp_sample_gauss_word(candidate)
+                                     : hp_sample_cbd_word(candidate);
 }
 
 // ---- the samplers on the host (hp_sample_host.cpp): what the kernels of hp_sample.hip write, word for word --------------------------------------
 namespace hpi {
-// kind: HP_SAMPLE_TERNARY or HP_SAMPLE_CBD; out [batch][L][N]: hp_sample_residue of scale * the sample of id stream + b * id_step in
+// kind: HP_SAMPLE_TERNARY, HP_SAMPLE_CBD or HP_SAMPLE_GAUSS; out [batch][L][N]: hp_sample_residue of scale * the sample of id stream + b * id_step in
 // every modulus -- the coefficient rows k_sample_spread writes, before the transform
 void sample_small_host(u32 kind, size_t logn, size_t L, const u64 *moduli, size_t batch, const uint8_t *seed, u64 stream, u64 id_step,
                        int64_t scale, u64 *out);
@@ -136,6 +163,6 @@ void sample_small_host(u32 kind, size_t logn, size_t L, const u64 *moduli, size_
 // goes to out + b * stride_words + m * N
 void sample_uniform_host(size_t logn, size_t L, const u64 *moduli, const u32 *limb_ids, size_t batch, const uint8_t *seed, u64 stream,
                          size_t stride_words, u64 *out);
-// kind: HP_SAMPLE_TERNARY or HP_SAMPLE_CBD; out [batch][N], every value times scale
+// kind: HP_SAMPLE_TERNARY, HP_SAMPLE_CBD or HP_SAMPLE_GAUSS; out [batch][N], every value times scale
 void sample_signed_host(u32 kind, size_t logn, size_t batch, const uint8_t *seed, u64 stream, int64_t scale, int64_t *out);
 } // namespace hpi

@@ -1,7 +1,7 @@
 // hp_sample.hip -- the device samplers (hp_dev_sample_*, the seeded key generators): a counter-based ChaCha20 keystream turned into
-// uniform residues, ternary and centred-binomial coefficients.  hp_sample.h has the stream layout and every rule; the kernels call
-// those functions as they are.  Further down, the kernels of the seeded ciphertext calls (hp_dev_sample_small_ntt,
-// hp_dev_rlwe_encrypt_seeded, hp_dev_rlwe_encrypt_pk_seeded) over the same blocks.
+// uniform residues, ternary, centred-binomial and discrete Gaussian coefficients.  hp_sample.h has the stream layout and every rule;
+// the kernels call those functions as they are.  Further down, the kernels of the seeded ciphertext calls
+// (hp_dev_sample_small_ntt, hp_dev_rlwe_encrypt_seeded, hp_dev_rlwe_encrypt_pk_seeded) over the same blocks.
 //
 // One thread = one ChaCha20 block = 8 consecutive coefficients of one row = 64 bytes, written as four non-temporal 16-byte stores
 // (written once, far more data than L2 holds).  Pure VALU: add / xor / rotate on 16 registers, no LDS, no inline assembly; seed,
@@ -78,10 +78,7 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) k_sample_signed(HpSampleSeed s
     hp_chacha20_block(st, o, RotV{});
     u64 w[8];
 #pragma unroll
-    for (u32 c = 0; c < 8; c++) {
-        const u64 v = hp_sample_candidate(o, c);
-        w[c] = (u64)(scale * (KIND == HP_SAMPLE_TERNARY ? hp_sample_ternary_word(v) : hp_sample_cbd_word(v)));
-    }
+    for (u32 c = 0; c < 8; c++) w[c] = (u64)(scale * hp_sample_small_word(KIND, hp_sample_candidate(o, c)));
     u64 *dst = reinterpret_cast<u64 *>(out) + (b << (logb + 3)) + ((u64)j << 3);
 #pragma unroll
     for (u32 c = 0; c < 8; c += 2) st_nt(dst + c, U2{w[c], w[c + 1]});
@@ -92,8 +89,8 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) k_sample_signed(HpSampleSeed s
 // registers while the thread walks the moduli -- no int64 row crosses HBM.  Polynomial p has the id stream + p * id_step and its
 // rows at out + p * pstride + m * N.  The forward transform reads the rows next: ordinary 16-byte stores.
 template <u32 KIND>
-__global__ void __launch_bounds__(SAMPLE_THREADS) k_sample_spread(HpSampleSeed seed, HpSampleRows rows, u32 L, u32 logb, u64 total, u64 stream,
-                                                                u64 id_step, long long scale, u64 pstride, u64 *__restrict__ out) {
+HP_DEV void sample_spread_item(const HpSampleSeed &seed, const HpSampleRows &rows, u32 L, u32 logb, u64 total, u64 stream, u64 id_step,
+                               long long scale, u64 pstride, u64 *__restrict__ out) {
     u64 p;
     u32 j;
     if (!sample_item(total, logb, p, j)) return;
@@ -109,6 +106,19 @@ __global__ void __launch_bounds__(SAMPLE_THREADS) k_sample_spread(HpSampleSeed s
 #pragma unroll
         for (u32 c = 0; c < 8; c += 2) *reinterpret_cast<U2 *>(dst + c) = U2{hp_sample_residue(v[c], q), hp_sample_residue(v[c + 1], q)};
     }
+}
+// ternary and centred binomial: what hp_dev_sample_small_ntt takes, and the errors of the default sampler
+template <u32 KIND>
+__global__ void __launch_bounds__(SAMPLE_THREADS) k_sample_spread(HpSampleSeed seed, HpSampleRows rows, u32 L, u32 logb, u64 total, u64 stream,
+                                                                u64 id_step, long long scale, u64 pstride, u64 *__restrict__ out) {
+    static_assert(KIND == HP_SAMPLE_TERNARY || KIND == HP_SAMPLE_CBD, "the Gaussian rows have a kernel of their own");
+    sample_spread_item<KIND>(seed, rows, L, logb, total, stream, id_step, scale, pstride, out);
+}
+// the error rows of the seeded ciphertext calls under the Gaussian error sampler (hp_ctx_set_error_sampler): the same thread, the
+// 30-entry compare chain of hp_sample_gauss_word in place of the popcounts
+__global__ void __launch_bounds__(SAMPLE_THREADS) k_gauss_spread(HpSampleSeed seed, HpSampleRows rows, u32 L, u32 logb, u64 total, u64 stream,
+                                                               u64 id_step, long long scale, u64 pstride, u64 *__restrict__ out) {
+    sample_spread_item<HP_SAMPLE_GAUSS>(seed, rows, L, logb, total, stream, id_step, scale, pstride, out);
 }
 
 // the 8 uniform words of block j of a row: k_sample_uniform's draw and bounded redraw loop, statement for statement (that kernel
@@ -247,6 +257,7 @@ hipError_t hp_launch_sample_signed(u32 kind, const HpSampleSeed &seed, u32 logn,
     const u64 total = batch << logb;
     if (kind == HP_SAMPLE_TERNARY) return sample_launch(k_sample_signed<HP_SAMPLE_TERNARY>, total, stream, seed, logb, total, stream_id, scale, out);
     if (kind == HP_SAMPLE_CBD) return sample_launch(k_sample_signed<HP_SAMPLE_CBD>, total, stream, seed, logb, total, stream_id, scale, out);
+    if (kind == HP_SAMPLE_GAUSS) return sample_launch(k_sample_signed<HP_SAMPLE_GAUSS>, total, stream, seed, logb, total, stream_id, scale, out);
     return hipErrorInvalidValue;
 }
 
@@ -259,6 +270,8 @@ hipError_t hp_launch_sample_spread(u32 kind, const HpSampleSeed &seed, const HpS
         return sample_launch(k_sample_spread<HP_SAMPLE_TERNARY>, total, stream, seed, rows, L, logb, total, stream_id, id_step, scale, pstride, out);
     if (kind == HP_SAMPLE_CBD)
         return sample_launch(k_sample_spread<HP_SAMPLE_CBD>, total, stream, seed, rows, L, logb, total, stream_id, id_step, scale, pstride, out);
+    if (kind == HP_SAMPLE_GAUSS)
+        return sample_launch(k_gauss_spread, total, stream, seed, rows, L, logb, total, stream_id, id_step, scale, pstride, out);
     return hipErrorInvalidValue;
 }
 

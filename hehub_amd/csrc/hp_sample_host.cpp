@@ -1,4 +1,4 @@
-// hp_sample_host.cpp -- the three samplers of hp_sample.h on the host: one ChaCha20 block per 8 coefficients, the rules of the header.
+// hp_sample_host.cpp -- the four samplers of hp_sample.h on the host: one ChaCha20 block per 8 coefficients, the rules of the header.
 // No HIP, no context; plain C++ (tests/cpp/sample_shim.cpp builds it with g++).  No entry point of the library calls these --
 // there is no CPU fallback -- they are what tests/test_sample_host.py holds against the Python model, rule by rule.
 #include "hp_sample.h"
@@ -33,8 +33,7 @@ void sample_signed_host(u32 kind, size_t logn, size_t batch, const uint8_t *seed
             hp_sample_state(sd, (u32)j, hp_sample_word13(0, kind, 0), stream + b, st);
             hp_chacha20_block(st, o, HpRotl{});
             for (u32 c = 0; c < 8; c++) {
-                const u64 v = hp_sample_candidate(o, c);
-                out[b * n + 8 * j + c] = scale * (kind == HP_SAMPLE_TERNARY ? hp_sample_ternary_word(v) : hp_sample_cbd_word(v));
+                out[b * n + 8 * j + c] = scale * hp_sample_small_word(kind, hp_sample_candidate(o, c));
             }
         }
 }

@@ -120,6 +120,14 @@ class Engine:
     def parity_level(self) -> str:
         return "BA"[self.lib.hp_ctx_get_parity_level(self.h)]
 
+    def set_error_sampler(self, kind: int):
+        """the error distribution of the seeded key and ciphertext calls: 3 (centred binomial, the default) or 4 (discrete Gaussian of
+        sigma 3.2); include/hehub_amd.h: hp_ctx_set_error_sampler.  A fork inherits it."""
+        self._chk(self.lib.hp_ctx_set_error_sampler(self.h, kind))
+
+    def get_error_sampler(self) -> int:
+        return int(self.lib.hp_ctx_get_error_sampler(self.h))
+
     def to_device(self, a: np.ndarray):
         assert a.dtype == np.uint64
         return self.torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).to(f"cuda:{self.device}")
@@ -734,9 +742,15 @@ class Engine:
         self._chk(self.lib.hp_dev_sample_cbd(self.h, logn, batch, self._seed(seed), stream, self._ptr(out)))
         return out
 
+    def sample_gauss(self, logn: int, seed: bytes, stream: int, batch: int = 1):
+        """discrete Gaussian coefficients, sigma = 3.2 (a 30-entry cumulative table: range +-30, variance 10.24) -> int64 [batch][n]"""
+        out = self.empty((batch, 1 << logn))
+        self._chk(self.lib.hp_dev_sample_gauss(self.h, logn, batch, self._seed(seed), stream, self._ptr(out)))
+        return out
+
     def hks_keygen_seeded(self, moduli_ext, k: int, alpha: int, s_to, s_from, seed: bytes, stream: int, error_scale: int = 1, out=None):
-        """hks_keygen on rows drawn on the device: for key r, digit d, a = the uniform sample and e = error_scale * the centred-binomial
-        sample of the polynomial id stream + r * dnum + d.  s_to [E][n], s_from [R][E][n] -> [R][dnum][2][E][n]."""
+        """hks_keygen on rows drawn on the device: for key r, digit d, a = the uniform sample and e = error_scale * the sample of the
+        context's error sampler (set_error_sampler: centred binomial by default) of the polynomial id stream + r * dnum + d.  s_to [E][n], s_from [R][E][n] -> [R][dnum][2][E][n]."""
         R, E, n = s_from.shape
         nd = (E - k + alpha - 1) // alpha
         out = self.empty((R, nd, 2, E, n)) if out is None else out
@@ -777,7 +791,7 @@ class Engine:
     def rlwe_encrypt_seeded(self, moduli, sk, pt, seed: bytes, stream: int, error_scale: int = 1, with_c1: bool = True, batch=None,
                             out=None):
         """secret-key encryption on rows drawn on the device: sk [L][n] (NTT form), pt [B][L][n] (coefficient form) or None (zero; then
-        `batch` ciphertexts).  Ciphertext b: a = the uniform, e = error_scale * the centred-binomial sample of the id stream + b;
+        `batch` ciphertexts).  Ciphertext b: a = the uniform, e = error_scale * the error sampler's sample of the id stream + b;
         -> [B][2][L][n] = (e + pt - a s, a), or with_c1 = False [B][L][n]: c0 alone, the ciphertext being c0 + (seed, stream).
         pt = None with c1 is a public key (e - a s, a).  Canonical words."""
         L, n = sk.shape
@@ -791,7 +805,7 @@ class Engine:
 
     def rlwe_encrypt_pk_seeded(self, moduli, pk, pt, seed: bytes, stream: int, error_scale: int = 1, batch=None, out=None):
         """public-key encryption: pk [2][L][n] (rlwe_encrypt_seeded with pt = None), pt [B][L][n] (coefficient form) or None.
-        Ciphertext b: u = the ternary sample of the id stream + 2b, e0, e1 = error_scale * the centred-binomial samples of stream + 2b,
+        Ciphertext b: u = the ternary sample of the id stream + 2b, e0, e1 = error_scale * the error sampler's samples of stream + 2b,
         stream + 2b + 1 -> [B][2][L][n] = (pk0 u + e0 + pt, pk1 u + e1), canonical words.  Ids stream .. stream + 2B - 1."""
         _, L, n = pk.shape
         B = pt.shape[0] if pt is not None else (1 if batch is None else batch)

@@ -83,7 +83,8 @@ void hp_ctx_destroy(hp_ctx *ctx);
  * src/circuits/linear_algebra.h:109-133, bench/benchmarks.cpp:24-35: one ciphertext fills 10 .. 100 of the 256 CUs, so independent
  * calls should overlap): a context with its own stream and scratch workspace whose calls run concurrently on the device with those
  * of its parent and siblings.  The family shares ONE lock (host-side enqueueing is serialised exactly as on a single context) and ONE
- * copy of the twiddle tables / per-chain constants / gather maps.  Knobs and parity level start as the parent's are at the fork.
+ * copy of the twiddle tables / per-chain constants / gather maps.  Knobs, parity level and error sampler start as the parent's are at
+ * the fork.
  * Destroy every member with hp_ctx_destroy (any order).  hp_ctx_wait_for is the ordering primitive between lanes: everything
  * `ctx` enqueues from now on runs after everything `other` has enqueued so far -- a device-side event, no host synchronisation.
  * Buffers are the caller's: a lane that reads what another lane wrote (or reuses memory another lane still reads) needs that
@@ -93,6 +94,12 @@ int hp_ctx_wait_for(hp_ctx *ctx, hp_ctx *other);
 typedef enum { HP_PARITY_B = 0, HP_PARITY_A = 1 } hp_parity_level;
 int hp_ctx_set_parity_level(hp_ctx *ctx, int level);
 int hp_ctx_get_parity_level(hp_ctx *ctx);
+/* The error distribution of the four seeded calls (hp_dev_hks_keygen_seeded, hp_dev_hks_keygen_rot_seeded, hp_dev_rlwe_encrypt_seeded,
+ * hp_dev_rlwe_encrypt_pk_seeded): a sampler kind of "Sampling on the device" below, 3 = centred binomial (the default) or 4 = discrete
+ * Gaussian of sigma 3.2; anything else is HP_EINVAL and leaves the setting as it was.  A setting of the context like the parity level
+ * (hp_ctx_fork copies it); no environment variable.  The getter returns the kind, HP_EINVAL on a NULL context. */
+int hp_ctx_set_error_sampler(hp_ctx *ctx, uint32_t kind);
+int hp_ctx_get_error_sampler(hp_ctx *ctx);
 const char *hp_last_error(hp_ctx *ctx);
 const char *hp_version(void);
 /* enqueue on an existing hipStream_t (e.g. torch's current stream); NULL = the HIP default stream.
@@ -769,10 +776,11 @@ int hp_dev_hks_keygen(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha
 int hp_dev_hks_keygen_rot(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t keys,
                           const size_t *steps, const unsigned char *conj, const uint64_t *d_s /* u64[L+k][N] */,
                           const uint64_t *d_a, const int64_t *d_e, uint64_t *d_keys);
-/* Sampling on the device: a counter-based ChaCha20 keystream (RFC 8439 section 2.3, 20 rounds) and three samplers over it.  Every
+/* Sampling on the device: a counter-based ChaCha20 keystream (RFC 8439 section 2.3, 20 rounds) and four samplers over it.  Every
  * output is a function of (seed, stream) alone -- no generator state, no host draws, nothing crossing PCIe -- and is pinned word for
- * word by tests/sample_model.py.  (hehub's samplers use a default-seeded std::default_random_engine and double arithmetic that is
- * not exact above 2^53; they are not reproduced.)
+ * word by tests/sample_model.py and tests/gauss_model.py.  (hehub's samplers use a default-seeded std::default_random_engine and double arithmetic that is
+ * not exact above 2^53; they are not reproduced: its rounded Gaussian, std::round of a std::normal_distribution draw, has no
+ * portable word-for-word definition, so the Gaussian below is an exact integer rule over the same stream.)
  *
  * The stream.  One block yields 16 output words o[0..15] and serves the 8 coefficients 8j .. 8j+7 of one row, so logn >= 3; its state:
  *     words 0-3    the four ChaCha constants
@@ -781,7 +789,7 @@ int hp_dev_hks_keygen_rot(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t a
  *     word  13     attempt (bits 0-15) | kind << 16 (bits 16-23) | limb_id << 24 (bits 24-31)
  *     words 14,15  low / high half of the 64-bit polynomial id
  * Coefficient 8j + c owns the candidate v_c = o[2c] | o[2c+1] << 32 (keystream bytes 8c .. 8c+7, little-endian).  The kind (1 uniform,
- * 2 ternary, 3 centred binomial) keeps the samplers from sharing keystream under one (seed, stream).  Polynomial b of a call has the
+ * 2 ternary, 3 centred binomial, 4 discrete Gaussian) keeps the samplers from sharing keystream under one (seed, stream).  Polynomial b of a call has the
  * id stream + b in 64-bit arithmetic.
  *   uniform, modulus q (2 <= q < 2^63): w = v_c & (2^bit_length(q) - 1), accepted when w < q; otherwise the same candidate position
  *     of the same block under attempt + 1.  Bounded: after 64 rejected attempts (0 .. 63; probability < 2^-64 per word, acceptance
@@ -789,15 +797,22 @@ int hp_dev_hks_keygen_rot(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t a
  *     row (uniform in either domain).  limb_id is the caller's label of the modulus, by default the row index.
  *   ternary (limb_id 0, attempt 0): the first of the 32 two-bit fields of v_c, from the low end, that is not 3, minus 1; 0 if all are 3.
  *   centred binomial, eta = 21 (limb_id 0, attempt 0): popcount(v_c & (2^21 - 1)) - popcount((v_c >> 21) & (2^21 - 1)): range +-21,
- *     variance 10.5 (sigma 3.24: hehub's default std_dev = 3.2 as an exact integer distribution).
+ *     variance 10.5 (sigma 3.24: close to hehub's default std_dev = 3.2, but a binomial, not a Gaussian).
+ *   discrete Gaussian, sigma = 16/5 (limb_id 0, attempt 0): the distribution D_{Z,3.2} of the HE security standard's tables, by a
+ *     cumulative table.  rho(k) = exp(-25 k^2 / 512), S = the sum of rho(k) over all integers k; a magnitude m has the probability
+ *     P(0) = rho(0) / S, P(m) = 2 rho(m) / S.  C[m] = floor(2^63 * (P(0) + ... + P(m))) for m = 0 .. 29 -- 30 entries, integer literals
+ *     of hp_sample.h; C[29] = 2^63 - 1, and so would every further entry be.  sign = v_c & 1, u = v_c >> 1 (63 bits),
+ *     m = #{ i in 0..29 : u >= C[i] }; the word is -m where sign = 1 and m != 0, else m.  Range +-30, variance 10.24, zero carries no
+ *     sign; statistical distance to D_{Z,3.2} below 2^-57.  One candidate per coefficient and all 30 compares whatever the value: the
+ *     work does not depend on what is drawn.
  *
  * hp_dev_sample_uniform: row m of polynomial b goes to d_out + b * stride + m * N words, stride = stride_words, or L * N where that
  * is 0; the words between the rows of two polynomials are not touched (uniform rows can be written straight into d_keys[r][d][1]).
- * hp_dev_sample_ternary / hp_dev_sample_cbd: i64[batch][N], for hp_dev_poly_from_signed or as error rows.
+ * hp_dev_sample_ternary / hp_dev_sample_cbd / hp_dev_sample_gauss: i64[batch][N], for hp_dev_poly_from_signed or as error rows.
  * HP_EINVAL before anything is enqueued: logn < 3 or above 16, L == 0 or L > 32, batch == 0, a modulus < 2 or >= 2^63, a limb id
  * >= 256, a stride that is odd or below L * N, a NULL seed or moduli, a device pointer that is NULL or not 16-byte aligned.
- * Out of scope: a wire kind for half keys; sparse / fixed-Hamming-weight secrets; discrete Gaussians; sampling inside the inner
- * product; the node, sharded and C++ host layers. */
+ * Out of scope: a wire kind for half keys; sparse / fixed-Hamming-weight secrets; discrete Gaussians of any other width, or from a
+ * run-time table; Gaussian secrets; sampling inside the inner product; the node, sharded and C++ host layers. */
 int hp_dev_sample_uniform(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli,
                           const uint32_t *limb_ids /* HOST, L entries < 256, NULL = 0..L-1 */, size_t batch,
                           const uint8_t *seed /* HOST, 32 bytes */, uint64_t stream,
@@ -805,15 +820,17 @@ int hp_dev_sample_uniform(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *mo
 int hp_dev_sample_ternary(hp_ctx *ctx, size_t logn, size_t batch, const uint8_t *seed, uint64_t stream,
                           int64_t *d_out /* i64[batch][N] */);
 int hp_dev_sample_cbd(hp_ctx *ctx, size_t logn, size_t batch, const uint8_t *seed, uint64_t stream, int64_t *d_out);
+int hp_dev_sample_gauss(hp_ctx *ctx, size_t logn, size_t batch, const uint8_t *seed, uint64_t stream, int64_t *d_out);
 /* The seeded key generators: hp_dev_hks_keygen / hp_dev_hks_keygen_rot on rows drawn here.  For key r, digit d, with the polynomial id
  * stream + r * dnum + d:  a[r][d] is the uniform sample over all L + k moduli with limb ids 0 .. L+k-1, e[r][d] is error_scale times
- * the centred-binomial sample (error_scale = 1 for CKKS, = t for BGV, whose keys need error rows t * e).  The key is word for word
+ * the sample of the context's error sampler (hp_ctx_set_error_sampler: centred binomial by default, or discrete Gaussian; error_scale
+ * = 1 for CKKS, = t for BGV, whose keys need error rows t * e).  The key is word for word
  * what the plain call writes for those rows: the samplers write a into the [1] halves and e into workspace, then the plain call's
  * in-place path (d_a == NULL) runs.  Workspace: keys * dnum * N words, whatever L and k are.
  * hp_dev_hks_key_expand rewrites only the [r][d][1] halves (a * 2^64 mod q_m, canonical) from (seed, stream) and leaves the [0]
  * halves as the caller loaded them: a key set can be stored or shipped as its [0] halves plus 40 bytes.
- * HP_EINVAL before anything is enqueued: logn < 3, a NULL seed, keys == 0, error_scale == 0 or >= 2^58 (21 * error_scale must fit an
- * int64_t); then everything the plain call refuses, with its code. */
+ * HP_EINVAL before anything is enqueued: logn < 3, a NULL seed, keys == 0, error_scale == 0 or >= 2^58 (21 * error_scale, or 30 * error_scale
+ * under the Gaussian sampler, must fit an int64_t); then everything the plain call refuses, with its code. */
 int hp_dev_hks_keygen_seeded(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t alpha, const uint64_t *moduli_ext, size_t keys,
                              const uint64_t *d_s_to, const uint64_t *d_s_from, const uint8_t *seed, uint64_t stream,
                              uint64_t error_scale, uint64_t *d_keys);
@@ -832,10 +849,12 @@ int hp_dev_hks_key_expand(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t a
  * the same polynomial, reduced below q_m -- without the int64 rows ever reaching memory: one thread turns a block into the
  * residues of its 8 coefficients in all L moduli (a coefficient v, |v| <= 21 * scale, maps to |v| mod q_m, negated to q_m - r where
  * v < 0 and r != 0), the forward transform and one reduction follow.  How a secret, or the u of a public-key encryption, gets to
- * the device from 40 bytes.  The call uses the ids stream .. stream + batch - 1.
+ * the device from 40 bytes.  The call uses the ids stream .. stream + batch - 1.  (Kind 4 is not taken here: Gaussian rows in NTT form
+ * are hp_dev_poly_from_signed of hp_dev_sample_gauss; the seeded calls below draw theirs in registers the same way as the binomial ones.)
  *
  * hp_dev_rlwe_encrypt_seeded: for ciphertext b, with the polynomial id stream + b:  a_b = the uniform sample over `moduli` with limb
- * ids 0 .. L-1, e_b = error_scale times the centred-binomial sample (the kind tag keeps the two apart), and
+ * ids 0 .. L-1, e_b = error_scale times the sample of the context's error sampler (hp_ctx_set_error_sampler; the kind tag
+ * keeps the two apart), and
  *     c1 = a_b        c0 = NTT(e_b) + NTT(pt_b) - a_b * s      (mod q_m)
  * error_scale = 1 is the CKKS form, error_scale = t the BGV form t * e - a * s + m.  d_pt is in coefficient form, hp_dev_ntt's input
  * contract; NULL is the zero plaintext.  The call uses the ids stream .. stream + batch - 1.
@@ -850,7 +869,8 @@ int hp_dev_hks_key_expand(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t a
  * Workspace: none when d_pt == NULL or with_c1 == 1 (NTT(pt) passes through the c1 rows); else batch * L * N words.
  *
  * hp_dev_rlwe_encrypt_pk_seeded: for ciphertext b:  u_b = the ternary sample of the id stream + 2b, e0_b = error_scale times the
- * centred-binomial sample of stream + 2b, e1_b = the same of stream + 2b + 1 (the kind tag keeps u_b and e0_b apart), and
+ * sample of the context's error sampler of stream + 2b, e1_b = the same of stream + 2b + 1 (the kind tag keeps u_b and e0_b apart; u_b
+ * is ternary whatever the error sampler), and
  *     ct0 = pk0 * NTT(u_b) + NTT(e0_b) + NTT(pt_b)        ct1 = pk1 * NTT(u_b) + NTT(e1_b)      (mod q_m)
  * The call uses the ids stream .. stream + 2 * batch - 1.  With pk = (e_pk - a * s, a) the ciphertext decrypts to pt plus
  * error_scale * (u * e_pk + e0 + e1 * s) -- pk generated with the same error_scale.  Workspace: at most 2 * batch * L * N words.
@@ -859,8 +879,8 @@ int hp_dev_hks_key_expand(hp_ctx *ctx, size_t logn, size_t L, size_t k, size_t a
  * hp_dev_rlwe_encrypt_core), a modulus < 2 or >= 2^63, a NULL seed, moduli, d_sk / d_pk, d_ct or d_out, a device pointer that is not
  * 16-byte aligned, a scale that is 0 or >= 2^58, a kind outside {2, 3}, with_c1 outside {0, 1}, d_ct overlapping d_sk, d_pk or
  * d_pt.  Chains that hp_dev_ntt refuses are refused with its code.
- * Out of scope: a wire kind for seeded ciphertexts; the node, sharded and C++ host layers; CKKS encoding; discrete Gaussians;
- * regenerating pk1 from a seed inside the public-key call. */
+ * Out of scope: a wire kind for seeded ciphertexts; the node, sharded and C++ host layers; CKKS encoding; discrete Gaussians of any
+ * other width, or from a run-time table; kind 4 in hp_dev_sample_small_ntt; regenerating pk1 from a seed inside the public-key call. */
 int hp_dev_sample_small_ntt(hp_ctx *ctx, size_t logn, size_t L, const uint64_t *moduli, size_t batch,
                             uint32_t kind /* 2 ternary, 3 centred binomial */, const uint8_t *seed /* HOST, 32 bytes */,
                             uint64_t stream, uint64_t scale, uint64_t *d_out /* u64[batch][L][N] */);
