@@ -128,6 +128,46 @@ HP_DEV const u64 *drop_addend_row(const u64 *addend, u32 add_poly_stride, u32 ad
                ? addend + ((size_t)(p2 >> 1) * add_ct_stride + (size_t)(p2 & 1) * add_poly_stride + k) * n : nullptr;
 }
 
+// ---- the blocks the inner products are made of (hp_ks.hip, hp_hks.hip, hp_lincomb.hip) -------------------------------------------
+// A thread owns two adjacent words of a row and one carry-save accumulator (HpAcc, hp_device.h) per word and output.
+// every HpAcc of an array of any rank
+HP_DEV void acc_zero(HpAcc &a) { hp_acc_zero(a); }
+template <class T, int N> HP_DEV void acc_zero(T (&a)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; i++) acc_zero(a[i]);
+}
+
+// one digit of a key-switch inner product: the key's two words of both halves (g0, g1), loaded once, times the digit's two words
+// d of a ciphertext into its acc[half][word] -- or of each of PT ciphertexts into acc[ciphertext][half][word]
+HP_DEV void key_mac(const U2 &g0, const U2 &g1, const U2 &d, HpAcc (&acc)[2][2]) {
+    const u64 kw[2][2] = {{g0.x, g0.y}, {g1.x, g1.y}};
+#pragma unroll
+    for (int h = 0; h < 2; h++) hp_mac2(acc[h][0], d.x, kw[h][0], acc[h][1], d.y, kw[h][1]);
+}
+template <int PT> HP_DEV void key_mac(const U2 &g0, const U2 &g1, const U2 (&d)[PT], HpAcc (&acc)[PT][2][2]) {
+    const u64 kw[2][2] = {{g0.x, g0.y}, {g1.x, g1.y}};
+#pragma unroll
+    for (int c = 0; c < PT; c++)
+#pragma unroll
+        for (int h = 0; h < 2; h++) hp_mac2(acc[c][h][0], d[c].x, kw[h][0], acc[c][h][1], d[c].y, kw[h][1]);
+}
+
+// The words (i, i + 1) of a row moved by a rotation: row[map[i]], row[map[i + 1]] -- one 8-byte load of the map's pair, then two
+// 8-byte loads -- or, map == NULL, the involution i -> n - 1 - i: the 16 bytes at n - 2 - i, swapped.  The loads are ordinary cached
+// ones: a moved row is read scattered, and again by every rotation.  map is wave-uniform (a kernel argument).
+struct MovedPair {
+    const u32 *map;
+    uint2 j;
+    HP_DEV MovedPair(const u32 *map, u32 n, u32 i) : map(map), j{n - 2 - i, 0} {
+        if (map) j = *reinterpret_cast<const uint2 *>(map + i);
+    }
+    HP_DEV U2 operator()(const u64 *row) const {
+        if (map) return U2{row[j.x], row[j.y]};
+        const U2 v = *reinterpret_cast<const U2 *>(row + j.x);
+        return U2{v.y, v.x};
+    }
+};
+
 // tail of the blocked inner products: the accumulators of two adjacent words -> two Montgomery words, for one 16-byte st_nt
 // (written once, read by the next kernel from HBM anyway: non-temporal, the key column keeps its place in L2)
 HP_DEV U2 acc2_montgomery(const HpAcc &a0, const HpAcc &a1, u64 q, u64 mqinv) {
@@ -135,4 +175,43 @@ HP_DEV U2 acc2_montgomery(const HpAcc &a0, const HpAcc &a1, u64 q, u64 mqinv) {
     hp_acc_value(a0, l0, h0);
     hp_acc_value(a1, l1, h1);
     return U2{hp_montgomery128_lazy(l0, h0, q, mqinv), hp_montgomery128_lazy(l1, h1, q, mqinv)};
+}
+// ... of PT ciphertexts x 2 halves, a key's 2^64 in every product: ciphertext p0 + c (those below P: a ragged last group skips the
+// rest) and half h go to the 16 bytes at dst + c * pstride + h * hstride (dst: where the kernel puts ciphertext p0, half 0)
+template <int PT>
+HP_DEV void acc_store_montgomery(const HpAcc (&acc)[PT][2][2], u32 p0, u32 P, u64 q, u64 mqinv, u64 *dst, size_t pstride, size_t hstride) {
+#pragma unroll
+    for (int c = 0; c < PT; c++) {
+        if (p0 + c < P) {
+#pragma unroll
+            for (int h = 0; h < 2; h++) {
+                const U2 v = acc2_montgomery(acc[c][h][0], acc[c][h][1], q, mqinv);
+                st_nt(dst + c * pstride + h * hstride, v);
+            }
+        }
+    }
+}
+
+// Tail of a sum of PLAIN products (no operand carries a 2^64: diagonals, tensor products): the one Montgomery reduction of the 128-bit
+// sum leaves a factor 2^-64, undone by a Harvey multiplication by 2^64 mod q with the limb's own pair (r64, r64h) -- hp_mul_hybrid_lazy's
+// tail: one high and two low products per OUTPUT word, no new constant, and below 2q for ANY 64-bit input, which is what the level-A
+// range guard and the drops ask of these rows.  (A Montgomery multiplication by 2^128 mod q costs one more product and a per-limb constant.)
+// Range: the Montgomery step returns hi + mulhi(u, q) + 1, so the sum's high half must stay at most 2^64 - 1 - q; how many terms
+// that allows is each caller's host formula (hp_drop.h).
+HP_DEV U2 acc2_plain(const HpAcc &a0, const HpAcc &a1, u64 q, u64 mqinv, u64 r64, u64 r64h) {
+    U2 v = acc2_montgomery(a0, a1, q, mqinv);   // the sum * 2^-64 ...
+    v.x = hp_harvey_lazy(v.x, r64, r64h, q);    // ... * 2^64, below 2q
+    v.y = hp_harvey_lazy(v.y, r64, r64h, q);
+    return v;
+}
+// ... to the 16 bytes at dst; add_prev: a later launch of a list longer than one table adds its word to the one the earlier launch
+// left (the contract is on residues, so the intermediate reductions are free)
+HP_DEV void acc_store_plain(const HpAcc &a0, const HpAcc &a1, u64 q, u64 mqinv, u64 two_q, u64 r64, u64 r64h, u32 add_prev, u64 *dst) {
+    U2 v = acc2_plain(a0, a1, q, mqinv, r64, r64h);
+    if (add_prev) {
+        const U2 old = *reinterpret_cast<const U2 *>(dst);
+        v.x = hp_add_lazy(v.x, old.x, two_q);
+        v.y = hp_add_lazy(v.y, old.y, two_q);
+    }
+    st_nt(dst, v);
 }

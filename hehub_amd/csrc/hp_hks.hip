@@ -75,6 +75,39 @@ hipError_t hp_launch_hks_modup(const HpLimb *limbs, const HpHksConsts *hc, u32 a
 // km = m + (m >= L ? KE - E : 0) belongs to modulus m of this level -- the ciphertext moduli first, the special primes last.  m is the
 // workgroup's, so km is one scalar; every internal row (digits, accumulators) stays indexed by m over E.  (hks_key_row: all inner kernels)
 __device__ __forceinline__ u32 hks_key_row(u32 m, u32 L, u32 E, u32 KE) { return m + (m >= L ? KE - E : 0u); }
+
+// The digit sum every inner product of this file is built on: acc[c][half][word] = sum_d D_c[d][m] * key[d][half][m] at the thread's
+// pair of words, for the PT polynomials c of the thread.  D_c[d][m] is the caller's own row own_row[c] where m belongs to digit d
+// (own: that digit; nd for a special prime, which belongs to none), else row (poly[c], d, m) of the lifted digits.
+// LD says how the words come in (its i: the thread's pair):
+//   HksStreamedPair  the digit pair at i, read once per launch: non-temporal; the key is shared by the whole batch: cached
+//   HksMovedPair     the digit pair moved by a rotation (MovedPair, hp_elem.h); the rotation's key is read once per launch: non-temporal
+// A kernel supplies its workgroup numbering (m, the polynomials, the chunk), the rows, and the tail: what becomes of acc.
+struct HksStreamedPair {
+    u32 i;
+    HP_DEV U2 key(const u64 *row) const { return *reinterpret_cast<const U2 *>(row + i); }
+    HP_DEV U2 digit(const u64 *row) const { return ld_nt(row + i); }
+};
+struct HksMovedPair {
+    u32 i;
+    MovedPair moved;
+    HP_DEV HksMovedPair(const u32 *map, u32 n, u32 i) : i(i), moved(map, n, i) {}
+    HP_DEV U2 key(const u64 *row) const { return ld_nt(row + i); }
+    HP_DEV U2 digit(const u64 *row) const { return moved(row); }
+};
+template <int PT, class LD>
+HP_DEV void hks_digit_sum(HpAcc (&acc)[PT][2][2], const LD &ld, const u64 *__restrict__ key, u32 KE, u32 km, u32 nd, u32 own,
+                          const u64 *const (&own_row)[PT], const u64 *__restrict__ lifted, const size_t (&poly)[PT], u32 E, u32 m, u32 n) {
+    acc_zero(acc);
+    for (u32 d = 0; d < nd; d++) {
+        const U2 g0 = ld.key(key + (((size_t)d * 2 + 0) * KE + km) * n);
+        const U2 g1 = ld.key(key + (((size_t)d * 2 + 1) * KE + km) * n);
+#pragma unroll
+        for (int c = 0; c < PT; c++)
+            key_mac(g0, g1, ld.digit((d == own) ? own_row[c] : lifted + ((poly[c] * nd + d) * E + m) * n), acc[c]);
+    }
+}
+
 template <int PT>
 __global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner(const HpLimb *__restrict__ limbs, u32 L, u32 E, u32 KE, u32 nd, u32 alpha, u32 P,
                                                           u32 n, u32 chunks, const u64 *__restrict__ lifted,
@@ -84,37 +117,18 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner(const HpLimb *__rest
     const ElemTile tile(n, chunks);
     const u32 m = tile.row / PG, p0 = (tile.row % PG) * PT, km = hks_key_row(m, L, E, KE);
     const u64 q = limbs[m].q, mqinv = limbs[m].mqinv;
-    const u32 own = (m < L) ? m / alpha : nd;   // the digit this modulus belongs to (none for the special primes)
+    const u32 own = (m < L) ? m / alpha : nd;
+    const u64 *own_row[PT];
+    size_t poly[PT];
+#pragma unroll
+    for (int c = 0; c < PT; c++) {
+        poly[c] = min(p0 + c, P - 1);   // a ragged last group re-reads its last ciphertext and skips the store
+        own_row[c] = pt + (poly[c] * pt_pstride + m) * n;
+    }
     for (const u32 i : tile.pairs()) {
-        HpAcc acc[PT][2][2];   // carry-save columns (hp_device.h)
-#pragma unroll
-        for (int c = 0; c < PT; c++)
-#pragma unroll
-            for (int h = 0; h < 2; h++) { hp_acc_zero(acc[c][h][0]); hp_acc_zero(acc[c][h][1]); }
-        for (u32 d = 0; d < nd; d++) {
-            const U2 g0 = *reinterpret_cast<const U2 *>(key + (((size_t)d * 2 + 0) * KE + km) * n + i);
-            const U2 g1 = *reinterpret_cast<const U2 *>(key + (((size_t)d * 2 + 1) * KE + km) * n + i);
-            const u64 kw[2][2] = {{g0.x, g0.y}, {g1.x, g1.y}};
-#pragma unroll
-            for (int c = 0; c < PT; c++) {
-                const u32 p = min(p0 + c, P - 1);
-                const u64 *src = (d == own) ? pt + ((size_t)p * pt_pstride + m) * n : lifted + (((size_t)p * nd + d) * E + m) * n;
-                const U2 t = ld_nt(src + i);
-#pragma unroll
-                for (int h = 0; h < 2; h++) hp_mac2(acc[c][h][0], t.x, kw[h][0], acc[c][h][1], t.y, kw[h][1]);
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < PT; c++) {
-            const u32 p = p0 + c;
-            if (p < P) {
-#pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    const U2 v = acc2_montgomery(acc[c][h][0], acc[c][h][1], q, mqinv);
-                    st_nt(out + (((size_t)p * 2 + h) * E + m) * n + i, v);
-                }
-            }
-        }
+        HpAcc acc[PT][2][2];
+        hks_digit_sum(acc, HksStreamedPair{i}, key, KE, km, nd, own, own_row, lifted, poly, E, m, n);
+        acc_store_montgomery(acc, p0, P, q, mqinv, out + ((size_t)p0 * 2 * E + m) * n + i, (size_t)2 * E * n, (size_t)E * n);
     }
 }
 
@@ -149,50 +163,20 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner_hoisted(const HpLimb
     const u32 m = unit / PG, p0 = (unit % PG) * PT, r = w / chunks, km = hks_key_row(m, L, E, KE);
     const ElemTile tile(ElemTile::At{unit, w % chunks}, n);
     const u64 q = limbs[m].q, mqinv = limbs[m].mqinv;
-    const u32 own = (m < L) ? m / alpha : nd;   // the digit this modulus belongs to (none for the special primes)
+    const u32 own = (m < L) ? m / alpha : nd;
     const u64 *__restrict__ key = tab.key[r];
-    const u32 *__restrict__ map = tab.map[r];   // NULL: the involution i -> n - 1 - i
+    const u32 *__restrict__ map = tab.map[r];   // NULL: the involution
+    const u64 *own_row[PT];
+    size_t poly[PT];
+#pragma unroll
+    for (int c = 0; c < PT; c++) {
+        poly[c] = min(p0 + c, P - 1);
+        own_row[c] = pt + (poly[c] * pt_pstride + m) * n;
+    }
     for (const u32 i : tile.pairs()) {
-        // where the two digit words come from: the map's pair, or (involution) the 16 bytes at n - 2 - i, swapped
-        uint2 j{n - 2 - i, 0};
-        if (map) j = *reinterpret_cast<const uint2 *>(map + i);
-        HpAcc acc[PT][2][2];   // carry-save columns (hp_device.h)
-#pragma unroll
-        for (int c = 0; c < PT; c++)
-#pragma unroll
-            for (int h = 0; h < 2; h++) { hp_acc_zero(acc[c][h][0]); hp_acc_zero(acc[c][h][1]); }
-        for (u32 d = 0; d < nd; d++) {
-            const U2 g0 = ld_nt(key + (((size_t)d * 2 + 0) * KE + km) * n + i);
-            const U2 g1 = ld_nt(key + (((size_t)d * 2 + 1) * KE + km) * n + i);
-            const u64 kw[2][2] = {{g0.x, g0.y}, {g1.x, g1.y}};
-#pragma unroll
-            for (int c = 0; c < PT; c++) {
-                const u32 p = min(p0 + c, P - 1);
-                const u64 *src = (d == own) ? pt + ((size_t)p * pt_pstride + m) * n : lifted + (((size_t)p * nd + d) * E + m) * n;
-                U2 t;
-                if (map) {
-                    t.x = src[j.x];
-                    t.y = src[j.y];
-                } else {
-                    const U2 v = *reinterpret_cast<const U2 *>(src + j.x);
-                    t.x = v.y;
-                    t.y = v.x;
-                }
-#pragma unroll
-                for (int h = 0; h < 2; h++) hp_mac2(acc[c][h][0], t.x, kw[h][0], acc[c][h][1], t.y, kw[h][1]);
-            }
-        }
-#pragma unroll
-        for (int c = 0; c < PT; c++) {
-            const u32 p = p0 + c;
-            if (p < P) {
-#pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    const U2 v = acc2_montgomery(acc[c][h][0], acc[c][h][1], q, mqinv);
-                    st_nt(out + ((((size_t)p * R + r) * 2 + h) * E + m) * n + i, v);
-                }
-            }
-        }
+        HpAcc acc[PT][2][2];
+        hks_digit_sum(acc, HksMovedPair(map, n, i), key, KE, km, nd, own, own_row, lifted, poly, E, m, n);
+        acc_store_montgomery(acc, p0, P, q, mqinv, out + ((((size_t)p0 * R + r) * 2) * E + m) * n + i, (size_t)R * 2 * E * n, (size_t)E * n);
     }
 }
 
@@ -209,14 +193,11 @@ hipError_t hp_launch_hks_inner_hoisted(const HpLimb *limbs, u32 L, u32 E, u32 KE
 }
 
 // Diagonal linear transform in the extended basis (hp_dev_ckks_lintrans_hks): k_hks_inner_hoisted with the rotation loop INSIDE the
-// thread.  A thread owns one pair of words of acc[b][.][m] and, for every rotation r of the table, runs the digit loop of the hoisted
-// kernel (the map's pair or the swapped 16 bytes of the involution; cached digit loads; non-temporal key loads), reduces the digit sum
-// to a word w_r (Montgomery: the keys carry the 2^64) and multiplies it by the diagonal's word into a SECOND set of carry-save columns:
+// thread.  A thread owns one pair of words of acc[b][.][m] and, for every rotation r of the table, runs the digit sum of the hoisted
+// kernel (hks_digit_sum over HksMovedPair), reduces it to a word w_r (Montgomery: the keys carry the 2^64) and multiplies it by the
+// diagonal's word into a SECOND set of carry-save columns:
 //   acc[b][h][m][i] = sum_r diag_r[m][i] * w_r,      w_r = montgomery_128( sum_d D[b][d][m][map_r(i)] * key_r[d][h][m][i] )
-// The diagonals are plain words, so the one Montgomery reduction of the outer sum leaves a factor 2^-64.  It is undone by a Harvey
-// multiplication by 2^64 mod q with the limb's own pair (r64, r64h) -- hp_mul_hybrid_lazy's tail: one high and two low products per
-// OUTPUT word, no new constant, and its result is below 2q for any 64-bit input, which is what the level-A range guard and the drops
-// ask of these rows.  (A Montgomery multiplication by 2^128 mod q costs one more product and a new per-limb constant.)
+// The diagonals are plain words: the outer sum ends in the tail of a sum of plain products (acc_store_plain, hp_elem.h), below 2q.
 // The c0 term of the rotation is folded in rather than kept as a third accumulator and an addend row: on polynomial 0 and the
 // ciphertext moduli the word (P mod q) * map_r(c0) is added to w_r before the diagonal multiplies it -- ModDown divides P out exactly
 // and the special-prime limbs see a multiple of P, i.e. nothing.  One gathered load and one Harvey product per rotation on 1/(2(1+k/L))
@@ -258,26 +239,25 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner_lintrans(const HpLim
     const ElemTile tile(ElemTile::At{unit, w % chunks}, n, HKS_LT_CHUNK);
     const u32 r_first = FLAV == HKS_LT_BABY ? w / chunks : 0, r_end = FLAV == HKS_LT_BABY ? r_first + 1 : R;
     const u64 q = limbs[m].q, mqinv = limbs[m].mqinv, two_q = limbs[m].two_q, r64 = limbs[m].r64, r64h = limbs[m].r64h;
-    const u32 own = (m < L) ? m / alpha : nd;   // the digit this modulus belongs to (none for the special primes)
+    const u32 own = (m < L) ? m / alpha : nd;
     const bool fold = m < L;                    // polynomial 0 of these rows takes the c0 term
     const u64 pm = fold ? hc->p_mod_q[m] : 0, pmh = fold ? hc->p_mod_q_h[m] : 0;
     for (const u32 i : tile.pairs()) {
         HpAcc sum[2][2];   // the outer sum over the rotations
-#pragma unroll
-        for (int h = 0; h < 2; h++) { hp_acc_zero(sum[h][0]); hp_acc_zero(sum[h][1]); }
+        acc_zero(sum);
         for (u32 r = r_first; r < r_end; r++) {
             const u64 *__restrict__ key = tab.key[r];
-            const u32 *__restrict__ map = tab.map[r];   // NULL: the involution i -> n - 1 - i
+            const u32 *__restrict__ map = tab.map[r];   // NULL: the involution
             const u64 *__restrict__ dg = FLAV == HKS_LT_FLAT ? tab.diag[r] : nullptr;   // NULL: the constant 1
-            const size_t pr = FLAV == HKS_LT_GIANT ? (size_t)p * Rtot + r : p;          // the polynomial rotation r reads
-            const u64 *__restrict__ c0row = ct + (pr * 2 * L + m) * n;   // a ciphertext is 2 L rows: c0, then c1
-            const u64 *__restrict__ c1row = c0row + (size_t)L * n;
+            const size_t pr[1] = {FLAV == HKS_LT_GIANT ? (size_t)p * Rtot + r : p};           // the polynomial rotation r reads
+            const u64 *__restrict__ c0row = ct + (pr[0] * 2 * L + m) * n;   // a ciphertext is 2 L rows: c0, then c1
+            const u64 *const c1row[1] = {c0row + (size_t)L * n};
             if (FLAV == HKS_LT_BABY && !key) {   // the identity baby
 #pragma unroll
                 for (int h = 0; h < 2; h++) {
                     U2 v{0, 0};
                     if (fold) {
-                        v = *reinterpret_cast<const U2 *>((h ? c1row : c0row) + i);
+                        v = *reinterpret_cast<const U2 *>((h ? c1row[0] : c0row) + i);
                         v.x = hp_harvey_lazy(v.x, pm, pmh, q);
                         v.y = hp_harvey_lazy(v.y, pm, pmh, q);
                     }
@@ -285,32 +265,16 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner_lintrans(const HpLim
                 }
                 continue;
             }
-            // where the two digit words come from: the map's pair, or (involution) the 16 bytes at n - 2 - i, swapped
-            uint2 j{n - 2 - i, 0};
-            if (map) j = *reinterpret_cast<const uint2 *>(map + i);
-            const auto moved = [&](const u64 *src) {
-                if (map) return U2{src[j.x], src[j.y]};
-                const U2 v = *reinterpret_cast<const U2 *>(src + j.x);
-                return U2{v.y, v.x};
-            };
+            const HksMovedPair ld(map, n, i);
             U2 dw{1, 1};
             if (dg) dw = *reinterpret_cast<const U2 *>(dg + (size_t)km * n + i);
             U2 c0{0, 0};
-            if (fold) c0 = moved(c0row);
-            HpAcc acc[2][2];   // carry-save columns (hp_device.h)
-#pragma unroll
-            for (int h = 0; h < 2; h++) { hp_acc_zero(acc[h][0]); hp_acc_zero(acc[h][1]); }
-            for (u32 d = 0; d < nd; d++) {
-                const U2 g0 = ld_nt(key + (((size_t)d * 2 + 0) * KE + km) * n + i);
-                const U2 g1 = ld_nt(key + (((size_t)d * 2 + 1) * KE + km) * n + i);
-                const u64 kw[2][2] = {{g0.x, g0.y}, {g1.x, g1.y}};
-                const U2 t = moved((d == own) ? c1row : lifted + ((pr * nd + d) * E + m) * n);
-#pragma unroll
-                for (int h = 0; h < 2; h++) hp_mac2(acc[h][0], t.x, kw[h][0], acc[h][1], t.y, kw[h][1]);
-            }
+            if (fold) c0 = ld.moved(c0row);
+            HpAcc acc[1][2][2];
+            hks_digit_sum(acc, ld, key, KE, km, nd, own, c1row, lifted, pr, E, m, n);
 #pragma unroll
             for (int h = 0; h < 2; h++) {
-                U2 v = acc2_montgomery(acc[h][0], acc[h][1], q, mqinv);
+                U2 v = acc2_montgomery(acc[0][h][0], acc[0][h][1], q, mqinv);
                 if (h == 0 && fold) {
                     v.x += hp_harvey_lazy(c0.x, pm, pmh, q);
                     v.y += hp_harvey_lazy(c0.y, pm, pmh, q);
@@ -321,18 +285,8 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_inner_lintrans(const HpLim
         }
         if (FLAV == HKS_LT_BABY) continue;
 #pragma unroll
-        for (int h = 0; h < 2; h++) {
-            u64 *dst = out + (((size_t)p * 2 + h) * E + m) * n + i;
-            U2 v = acc2_montgomery(sum[h][0], sum[h][1], q, mqinv);   // the sum * 2^-64 ...
-            v.x = hp_harvey_lazy(v.x, r64, r64h, q);                  // ... * 2^64, below 2q
-            v.y = hp_harvey_lazy(v.y, r64, r64h, q);
-            if (add_prev) {
-                const U2 old = *reinterpret_cast<const U2 *>(dst);
-                v.x = hp_add_lazy(v.x, old.x, two_q);
-                v.y = hp_add_lazy(v.y, old.y, two_q);
-            }
-            st_nt(dst, v);
-        }
+        for (int h = 0; h < 2; h++)
+            acc_store_plain(sum[h][0], sum[h][1], q, mqinv, two_q, r64, r64h, add_prev, out + (((size_t)p * 2 + h) * E + m) * n + i);
     }
 }
 
@@ -363,8 +317,8 @@ hipError_t hp_launch_hks_bsgs_giants(const HpLimb *limbs, const HpHksConsts *hc,
 // kernel with the inner product already done (the baby rows).  A thread owns one pair of words of (b, m) for BOTH halves -- one
 // diagonal load serves h = 0 and h = 1 -- and a tile of GT giants: a baby pair is loaded once per tile, so a baby row is read
 // ceil(giants / GT) times per launch (ordinary cached loads), a diagonal word once per call (non-temporal).  The table is a kernel
-// argument: an absent diagonal is a NULL that the whole wave sees, and costs no load.  The tail is the flat kernel's: one Montgomery
-// reduction of the 128-bit sum, then the Harvey multiplication by 2^64 mod q, below 2q.  Ranges: a baby word is below the flat
+// argument: an absent diagonal is a NULL that the whole wave sees, and costs no load.  The tail is the flat kernel's
+// (acc_store_plain).  Ranges: a baby word is below the flat
 // kernel's bound for w_r plus the folded word, a diagonal word below 2q, `babies` of them per launch (hpi::hks_bsgs_plan).
 // GT = 4: 16 accumulators of 8 VGPRs; the counts are in DESIGN 4.7b (tests/test_bsgs_resources.py prints them).
 // Workgroups: row = ((b * E + m) * tiles + tile), plain numbering -- the tiles of one (b, m) read the same baby rows and are
@@ -382,10 +336,7 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_bsgs_presum(const HpLimb *
     const u64 *__restrict__ brow = baby + (size_t)b * baby_pstride + (size_t)m * n;   // baby i, half h: + (i * 2 + h) * E * n
     for (const u32 i : tile.pairs()) {
         HpAcc sum[GT][2][2];
-#pragma unroll
-        for (int c = 0; c < GT; c++)
-#pragma unroll
-            for (int h = 0; h < 2; h++) { hp_acc_zero(sum[c][h][0]); hp_acc_zero(sum[c][h][1]); }
+        acc_zero(sum);
         for (u32 j = 0; j < Bn; j++) {
             const U2 v0 = *reinterpret_cast<const U2 *>(brow + ((size_t)j * 2 + 0) * E * n + i);
             const U2 v1 = *reinterpret_cast<const U2 *>(brow + ((size_t)j * 2 + 1) * E * n + i);
@@ -403,18 +354,9 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_bsgs_presum(const HpLimb *
         for (int c = 0; c < GT; c++) {
             if (g0 + c < G) {
 #pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    u64 *dst = tab.dst[g0 + c] + (size_t)b * dst_pstride + ((size_t)h * E + m) * n + i;
-                    U2 v = acc2_montgomery(sum[c][h][0], sum[c][h][1], q, mqinv);   // the sum * 2^-64 ...
-                    v.x = hp_harvey_lazy(v.x, r64, r64h, q);                        // ... * 2^64, below 2q
-                    v.y = hp_harvey_lazy(v.y, r64, r64h, q);
-                    if (add_prev) {
-                        const U2 old = *reinterpret_cast<const U2 *>(dst);
-                        v.x = hp_add_lazy(v.x, old.x, two_q);
-                        v.y = hp_add_lazy(v.y, old.y, two_q);
-                    }
-                    st_nt(dst, v);
-                }
+                for (int h = 0; h < 2; h++)
+                    acc_store_plain(sum[c][h][0], sum[c][h][1], q, mqinv, two_q, r64, r64h, add_prev,
+                                    tab.dst[g0 + c] + (size_t)b * dst_pstride + ((size_t)h * E + m) * n + i);
             }
         }
     }
@@ -440,9 +382,9 @@ hipError_t hp_launch_hks_bsgs_presum(const HpLimb *limbs, u32 L, u32 E, u32 KE, 
 // 2q for any 64-bit operand, the lazy sums stay there, and one conditional subtraction ends each row.
 // A thread reads every word of key[..][0] and key[..][1] before it writes it: no scratch copy of the error rows, a may be in place.
 // Traffic: e, a and the two key rows are streamed (non-temporal, 16 bytes per lane); s_to[m] is shared by the R * nd rows of its
-// modulus and is left to the caches.  ROT: from_r = move_r(s_to), read through the rotation's map (or, the involution, the 16 bytes
-// at n - 2 - i swapped) as k_hks_inner_hoisted reads its digit rows -- the row is s_to[m] again, so the scattered reads hit what the
-// whole launch keeps in cache; otherwise s_from[r][m], read once per call: streamed.
+// modulus and is left to the caches.  ROT: from_r = move_r(s_to), read as k_hks_inner_hoisted reads its digit rows (MovedPair,
+// hp_elem.h) -- the row is s_to[m] again, so the scattered reads hit what the whole launch keeps in cache; otherwise s_from[r][m],
+// read once per call: streamed.
 template <bool ROT>
 __global__ void __launch_bounds__(ELEM_THREADS) k_hks_keygen(const HpLimb *__restrict__ limbs, const HpHksConsts *__restrict__ hc, u32 n,
                                                            u32 chunks, const u64 *__restrict__ s_to, const u64 *__restrict__ s_from,
@@ -457,10 +399,11 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_keygen(const HpLimb *__res
     const u64 *ar = a ? a + (size_t)tile.row * n : k1;
     const u64 *st = s_to + (size_t)m * n;
     const u64 *sf = ROT ? st : s_from + ((size_t)r * E + m) * n;
-    const u32 *__restrict__ map = ROT ? maps.map[r] : nullptr;   // ROT, NULL: the involution i -> n - 1 - i
+    const u32 *__restrict__ map = ROT ? maps.map[r] : nullptr;   // ROT, NULL: the involution
     const auto from = [&](u32 i) {
         if (!own) return U2{0, 0};
         if (!ROT) return ld_nt(sf + i);
+        // MovedPair's loads, written out: through the helper the kernel takes 104 VGPRs for 98, a wave per SIMD
         if (map) {
             const uint2 j = *reinterpret_cast<const uint2 *>(map + i);
             return U2{sf[j.x], sf[j.y]};
@@ -515,72 +458,30 @@ hipError_t hp_launch_hks_keygen(const HpLimb *limbs, const HpHksConsts *hc, u32 
 
 // ModDown conversion: Garner digits of the special-prime part once per coefficient, then its exact centred value
 // (x below floor(P/2), x - P from there on; an exact multiple of q_i above the half comes out as q_i, a representative
-// of 0) in every ciphertext modulus
-template <int K>
-__global__ void __launch_bounds__(ELEM_THREADS) k_hks_moddown(const HpLimb *__restrict__ limbs, const HpHksConsts *__restrict__ hc,
-                                                            u32 n, u32 chunks, const u64 *__restrict__ yp, u64 *__restrict__ rem) {
-    const u32 L = hc->L;
-    const ElemTile tile(n, chunks);   // row = p2
-    const u32 p2 = tile.row;
-    const u64 *src = yp + (size_t)p2 * K * n;
-    u64 *dst = rem + (size_t)p2 * L * n;
-    for (const u32 i : tile.words()) {
-        u64 v[K][1];
-#pragma unroll
-        for (int a = 0; a < K; a++) {
-            v[a][0] = src[(size_t)a * n + i];
-            garner_digit<K>(v[a], v, a, limbs[L + a].q, limbs[L + a].barrett_c, hc->pg_inv, hc->pg_inv_h);
-        }
-        const bool below = garner_below<K>(v, 0, K, hc->p_half);
-        for (u32 m = 0; m < L; m++) {
-            const u64 qm = limbs[m].q;
-            u64 r = 0;
-#pragma unroll
-            for (int a = 0; a < K; a++) {
-                r += hp_strict(hp_harvey_lazy(v[a][0], hc->p_pref[m][a], hc->p_pref_h[m][a], qm), qm);
-                r -= (r >= qm) ? qm : 0;
-            }
-            if (!below) {
-                u64 abs = hc->p_mod_q[m] + qm - r;
-                abs -= (abs >= qm) ? qm : 0;
-                r = qm - abs;
-            }
-            dst[(size_t)m * n + i] = r;
-        }
-    }
-}
-
-hipError_t hp_launch_hks_moddown(const HpLimb *limbs, const HpHksConsts *hc, u32 k, u32 n, u32 P2, const u64 *yp, u64 *rem,
-                                 hipStream_t stream) {
-    return elem_with_1to8(k, [&](auto kk) {
-        return elem_launch(k_hks_moddown<decltype(kk)::value>, P2, n, stream, limbs, hc, n, ElemChunks{}, yp, rem);
-    });
-}
-
-// ModDown with a plain modulus t (BGV; hehub_amd.h has the convention): the remainder is delta = t * c, c the centred value of
+// of 0) in every ciphertext modulus.
+// PLAIN: with a plain modulus t (BGV; hehub_amd.h has the convention) the remainder is delta = t * c, c the centred value of
 // u = [x]_P * t^-1 mod P -- delta = x mod P, delta = 0 mod t, |delta| <= t (P + 1) / 2 -- so that (x - delta) / P keeps x's value mod t.
-// k_hks_moddown with two multiplications more: every special-prime residue by t^-1 mod p_a (strict) before the Garner digits, the
-// centred residue by t mod q_m (Harvey, strict: the representative q_m of 0 becomes 0) before the store.  Words below q_m: what
-// down() and the fused drops take from k_hks_moddown.  The t-dependent constants are the by-value argument pc -- HpHksConsts
-// belongs to the chain alone.  Register budget (tests/test_hks_bgv_resources.py): no scratch, and the occupancy of k_hks_moddown<K>.
-template <int K>
-__global__ void __launch_bounds__(ELEM_THREADS) k_hks_moddown_t(const HpLimb *__restrict__ limbs, const HpHksConsts *__restrict__ hc,
-                                                              HpHksPlain pc, u32 n, u32 chunks, const u64 *__restrict__ yp,
-                                                              u64 *__restrict__ rem) {
+// Two multiplications more: every special-prime residue by t^-1 mod p_a (strict) before the Garner digits, the centred residue by
+// t mod q_m (Harvey, strict: the representative q_m of 0 becomes 0) before the store.  Words below q_m either way: what down() and
+// the fused drops take.  The t-dependent constants are pc, a by-value kernel argument -- HpHksConsts belongs to the chain alone.
+template <int K, bool PLAIN>
+HP_DEV void hks_moddown_body(const HpLimb *__restrict__ limbs, const HpHksConsts *__restrict__ hc, const HpHksPlain *pc, u32 n, u32 chunks,
+                             const u64 *__restrict__ yp, u64 *__restrict__ rem) {
     const u32 L = hc->L;
     const ElemTile tile(n, chunks);   // row = p2
     const u32 p2 = tile.row;
     const u64 *src = yp + (size_t)p2 * K * n;
     u64 *dst = rem + (size_t)p2 * L * n;
     for (const u32 i : tile.words()) {
-        // K >= 4: the Garner tables are read anew for every word (scalar loads, the constant cache) rather than hoisted out of this
-        // loop and spilled -- with pc's words on top of k_hks_moddown's that costs a wave per SIMD at K = 4 and scratch from K = 6 on
-        if constexpr (K >= 4) asm volatile("" : "+s"(hc));
+        // PLAIN, K >= 4: the Garner tables are read anew for every word (scalar loads, the constant cache) rather than hoisted out of this
+        // loop and spilled -- with pc's words on top of the rest that costs a wave per SIMD at K = 4 and scratch from K = 6 on
+        if constexpr (PLAIN && K >= 4) asm volatile("" : "+s"(hc));
         u64 v[K][1];
 #pragma unroll
         for (int a = 0; a < K; a++) {
             const u64 pa = limbs[L + a].q;
-            v[a][0] = hp_strict(hp_harvey_lazy(src[(size_t)a * n + i], pc.tinv_p[a], pc.tinv_p_h[a], pa), pa);
+            v[a][0] = src[(size_t)a * n + i];
+            if constexpr (PLAIN) v[a][0] = hp_strict(hp_harvey_lazy(v[a][0], pc->tinv_p[a], pc->tinv_p_h[a], pa), pa);
             garner_digit<K>(v[a], v, a, pa, limbs[L + a].barrett_c, hc->pg_inv, hc->pg_inv_h);
         }
         const bool below = garner_below<K>(v, 0, K, hc->p_half);
@@ -597,9 +498,31 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_hks_moddown_t(const HpLimb *__
                 abs -= (abs >= qm) ? qm : 0;
                 r = qm - abs;
             }
-            dst[(size_t)m * n + i] = hp_strict(hp_harvey_lazy(r, pc.t_mod_q[m], pc.t_mod_q_h[m], qm), qm);
+            if constexpr (PLAIN) r = hp_strict(hp_harvey_lazy(r, pc->t_mod_q[m], pc->t_mod_q_h[m], qm), qm);
+            dst[(size_t)m * n + i] = r;
         }
     }
+}
+template <int K>
+__global__ void __launch_bounds__(ELEM_THREADS) k_hks_moddown(const HpLimb *__restrict__ limbs, const HpHksConsts *__restrict__ hc,
+                                                            u32 n, u32 chunks, const u64 *__restrict__ yp, u64 *__restrict__ rem) {
+    hks_moddown_body<K, false>(limbs, hc, nullptr, n, chunks, yp, rem);
+}
+
+hipError_t hp_launch_hks_moddown(const HpLimb *limbs, const HpHksConsts *hc, u32 k, u32 n, u32 P2, const u64 *yp, u64 *rem,
+                                 hipStream_t stream) {
+    return elem_with_1to8(k, [&](auto kk) {
+        return elem_launch(k_hks_moddown<decltype(kk)::value>, P2, n, stream, limbs, hc, n, ElemChunks{}, yp, rem);
+    });
+}
+
+// ModDown with a plain modulus t: the PLAIN body.  Register budget (tests/test_hks_bgv_resources.py): no scratch, and the occupancy
+// of k_hks_moddown<K>.
+template <int K>
+__global__ void __launch_bounds__(ELEM_THREADS) k_hks_moddown_t(const HpLimb *__restrict__ limbs, const HpHksConsts *__restrict__ hc,
+                                                              HpHksPlain pc, u32 n, u32 chunks, const u64 *__restrict__ yp,
+                                                              u64 *__restrict__ rem) {
+    hks_moddown_body<K, true>(limbs, hc, &pc, n, chunks, yp, rem);
 }
 
 hipError_t hp_launch_hks_moddown_t(const HpLimb *limbs, const HpHksConsts *hc, const HpHksPlain &pc, u32 k, u32 n, u32 P2, const u64 *yp,

@@ -73,22 +73,17 @@ hipError_t hp_launch_tensor_rows(const HpLimb *limbs, u32 L, u32 k_first, u32 kc
 // quad = (sum_t a0 b0, sum_t (a0 b1 + a1 b0), sum_t a1 b1) over the terms of the table, for lazy relinearisation: everything after the
 // tensor product is linear in the quadratic ciphertext, so T products pay ONE key switch.  A thread owns one pair of words of a row
 // (p, limb), as in k_tensor, and keeps them for every term: six carry-save accumulators (three outputs x two words), per term four
-// 16-byte non-temporal loads (every operand word is read once per call) and four hp_mac2, and after the last term ONE Montgomery
-// reduction per output word.  The operands are plain words, so that reduction leaves a factor 2^-64: undone by the Harvey
-// multiplication by 2^64 mod q with the limb's own pair (r64, r64h) -- the tail of k_hks_inner_lintrans (hp_hks.hip): below 2q for any
-// 64-bit input, no new constant.  HBM traffic per output word: 32 T + 24 bytes, against (56 + 24 + 24) T for T launches of k_tensor
-// and a fold of their rows.
-// Range: operand words below 2q, the d1 column with two products per term: a launch of T terms sums at most 2 T (2q - 1)^2, and the
-// Montgomery step returns hi + mulhi(u, q) + 1, so hi must stay at most 2^64 - 1 - q: the host keeps T within that
-// (hpi::tensor_sum_max_terms, hp_drop.h: the whole table for every modulus the transforms accept).  A larger operand word can wrap
-// the sums unnoticed.  A longer list takes one launch per table; a later launch adds its reduced word to the word the earlier one left
-// (add_prev) -- the contract is on residues, so the intermediate reductions are free.
+// 16-byte non-temporal loads (every operand word is read once per call) and four hp_mac2, and after the last term the tail of a sum
+// of plain products (acc_store_plain, hp_elem.h): ONE Montgomery reduction per output word.  HBM traffic per output word: 32 T + 24
+// bytes, against (56 + 24 + 24) T for T launches of k_tensor and a fold of their rows.
+// Range: operand words below 2q, the d1 column with two products per term: a launch of T terms sums at most 2 T (2q - 1)^2, which the
+// host keeps within the tail's limit (hpi::tensor_sum_max_terms, hp_drop.h: the whole table for every modulus the transforms accept).
+// A larger operand word can wrap the sums unnoticed.  A longer list takes one launch per table, the later ones with add_prev.
 // TWO: the lane's words i, i + 1 (16-byte accesses); else the single last word of an odd row
 template <bool TWO>
 HP_DEV void tensor_sum_words(const HpLimb &m, const HpTensorSumTable &tab, size_t at, size_t poly, u32 add_prev, u64 *d0) {
     HpAcc s[3][2];   // [output][word]
-#pragma unroll
-    for (int c = 0; c < 3; c++) { hp_acc_zero(s[c][0]); hp_acc_zero(s[c][1]); }
+    acc_zero(s);
     for (u32 t = 0; t < tab.terms; t++) {
         const u64 *a0 = tab.a[t] + at, *b0 = tab.b[t] + at;
         U2 va0, va1, vb0, vb1;
@@ -107,18 +102,11 @@ HP_DEV void tensor_sum_words(const HpLimb &m, const HpTensorSumTable &tab, size_
 #pragma unroll
     for (int c = 0; c < 3; c++) {
         u64 *dst = d0 + (size_t)c * poly;
-        U2 v = acc2_montgomery(s[c][0], s[c][1], m.q, m.mqinv);   // the sum * 2^-64 ...
-        v.x = hp_harvey_lazy(v.x, m.r64, m.r64h, m.q);            // ... * 2^64, below 2q
-        v.y = hp_harvey_lazy(v.y, m.r64, m.r64h, m.q);
         if (TWO) {
-            if (add_prev) {
-                const U2 old = *reinterpret_cast<const U2 *>(dst);
-                v.x = hp_add_lazy(v.x, old.x, m.two_q);
-                v.y = hp_add_lazy(v.y, old.y, m.two_q);
-            }
-            st_nt(dst, v);
+            acc_store_plain(s[c][0], s[c][1], m.q, m.mqinv, m.two_q, m.r64, m.r64h, add_prev, dst);
         } else {
-            dst[0] = add_prev ? hp_add_lazy(v.x, dst[0], m.two_q) : v.x;
+            const u64 v = acc2_plain(s[c][0], s[c][1], m.q, m.mqinv, m.r64, m.r64h).x;
+            dst[0] = add_prev ? hp_add_lazy(v, dst[0], m.two_q) : v;
         }
     }
 }
@@ -248,14 +236,6 @@ HP_DEV __amdgpu_buffer_rsrc_t ks_rsrc(const void *base) {
 }
 HP_DEV U2 ks_u2(const v4u &v) { return U2{((u64)v.y << 32) | v.x, ((u64)v.w << 32) | v.z}; }
 
-template <int PT> HP_DEV void ks_mac(const KsRow<PT> &r, HpAcc (&acc)[PT][2][2]) {
-    const u64 kw[2][2] = {{r.g0.x, r.g0.y}, {r.g1.x, r.g1.y}};
-#pragma unroll
-    for (int c = 0; c < PT; c++)
-#pragma unroll
-        for (int h = 0; h < 2; h++) hp_mac2(acc[c][h][0], r.d[c].x, kw[h][0], acc[c][h][1], r.d[c].y, kw[h][1]);
-}
-
 // PACK: 48 / 40 = the digit rows of this output modulus are in the HP_PACK48 / HP_PACK40 format (hp_device.h); 0 = plain words
 template <int PT, int PACK>
 HP_DEV void ks_sweep(const __amdgpu_buffer_rsrc_t (&rd)[PT], const __amdgpu_buffer_rsrc_t (&rp)[PT], __amdgpu_buffer_rsrc_t rk,
@@ -297,11 +277,11 @@ HP_DEV void ks_sweep(const __amdgpu_buffer_rsrc_t (&rd)[PT], const __amdgpu_buff
         for (int c = 0; c < PT; c++) rb.d[c] = ks_u2(__builtin_amdgcn_raw_buffer_load_b128(rp[c], v16, 0, KS_NT));
     }
     auto mac_digit = [&](const KsRow<PT> &r) {
-        ks_mac<PT>(r, acc);
+        key_mac(r.g0, r.g1, r.d, acc);
         if (PACK == 40) { ksum[0][0] += r.g0.x; ksum[0][1] += r.g0.y; ksum[1][0] += r.g1.x; ksum[1][1] += r.g1.y; }
     };
     if (T) load_digit(ra, 0);
-    if (diag) ks_mac<PT>(rb, acc);
+    if (diag) key_mac(rb.g0, rb.g1, rb.d, acc);
     if (!T) return;
     u32 t = 0;
     for (; t + 2 <= T; t += 2) {
@@ -348,24 +328,11 @@ __global__ void __launch_bounds__(ELEM_THREADS) k_ks_inner_blk(const HpLimb *__r
     const u32 d_stride = (Le * n) << 3, k_half = (key_Le * n) << 3, k_stride = k_half << 1;
     for (const u32 i : tile.pairs()) {
         HpAcc acc[PT][2][2];   // [ciphertext][half][word]
-#pragma unroll
-        for (int c = 0; c < PT; c++)
-#pragma unroll
-            for (int h = 0; h < 2; h++) { hp_acc_zero(acc[c][h][0]); hp_acc_zero(acc[c][h][1]); }
+        acc_zero(acc);
         if (P40 && packed40) ks_sweep<PT, 40>(rd, rp, rk, i, n, L, k, d_stride, k_stride, k_half, q, acc);
         else if (packed) ks_sweep<PT, 48>(rd, rp, rk, i, n, L, k, d_stride, k_stride, k_half, q, acc);
         else ks_sweep<PT, 0>(rd, rp, rk, i, n, L, k, d_stride, k_stride, k_half, q, acc);
-#pragma unroll
-        for (int c = 0; c < PT; c++) {
-            const u32 p = p0 + c;
-            if (p < P) {
-#pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    const U2 v = acc2_montgomery(acc[c][h][0], acc[c][h][1], q, mqinv);
-                    st_nt(out + (((size_t)p * 2 + h) * Le + k) * n + i, v);
-                }
-            }
-        }
+        acc_store_montgomery(acc, p0, P, q, mqinv, out + ((size_t)p0 * 2 * Le + k) * n + i, (size_t)2 * Le * n, (size_t)Le * n);
     }
 }
 

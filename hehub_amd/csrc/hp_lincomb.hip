@@ -6,14 +6,13 @@
 // Every term is a ciphertext batch of its OWN limb count (tab.limbs[j] >= L rows per polynomial) read in its first L limb rows: the
 // mod-drop of a polynomial evaluation costs no copy.  A thread owns pairs of adjacent words of a row (b, h, m) and keeps one
 // carry-save accumulator per word for every term: per term one 16-byte non-temporal load per pair (the loads of a round are issued
-// together, then its hp_mac2) and after the last term ONE Montgomery reduction per output word -- the tail of k_tensor_sum
-// (hp_ks.hip): the coefficients are plain residues, so the Montgomery step leaves a factor 2^-64, undone by the Harvey multiplication
-// by 2^64 mod q with the limb's own pair (r64, r64h), below 2q for any 64-bit input; one conditional subtraction makes the word
-// canonical.  HBM traffic per output word: 8 (terms + 1) bytes (+ 8 with accumulate), against 16 + 24 = 40 bytes per term for a
-// scalar multiplication and an addition.
+// together, then its hp_mac2) and after the last term ONE Montgomery reduction per output word: the coefficients are plain residues,
+// so the tail is that of a sum of plain products (acc2_plain, hp_elem.h, has the argument) with the constant and the accumulated
+// word added BEFORE the reduction and one conditional subtraction after it, which makes the word canonical.  HBM traffic per output
+// word: 8 (terms + 1) bytes (+ 8 with accumulate), against 16 + 24 = 40 bytes per term for a scalar multiplication and an addition.
 // Range: operand words below 2q, coefficients and the constant below q, an accumulated word below 2q: a launch of T terms sums at
-// most T (q - 1)(2q - 1) + 3q, and the Montgomery step returns hi + mulhi(u, q) + 1, so hi must stay at most 2^64 - 1 - q: the host
-// keeps T within that (hpi::lincomb_max_terms, hp_drop.h).  A longer list takes one launch per table, the later ones with accumulate.
+// most T (q - 1)(2q - 1) + 3q, which the host keeps within the tail's limit (hpi::lincomb_max_terms, hp_drop.h).  A longer list takes
+// one launch per table, the later ones with accumulate.
 // The coefficients of a launch live in device memory, u64[terms + 1][L] (row `terms`: the constant): wave-uniform scalar loads.
 #include "hp_elem.h"
 
@@ -23,8 +22,7 @@ template <int R, bool TWO>
 HP_DEV void lincomb_words(const HpLimb &m, const HpLincombTable &tab, const u64 *__restrict__ coef, u32 L, u32 k, u32 n, size_t p2,
                           size_t at, u64 cst, u32 accumulate, u64 *dst) {
     HpAcc s[R][2];
-#pragma unroll
-    for (int t = 0; t < R; t++) { hp_acc_zero(s[t][0]); hp_acc_zero(s[t][1]); }
+    acc_zero(s);
     for (u32 j = 0; j < tab.terms; j++) {
         const u64 c = coef[(size_t)j * L + k];
         const u64 *x = tab.src[j] + (p2 * tab.limbs[j] + k) * n + at;
