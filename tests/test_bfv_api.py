@@ -1,15 +1,13 @@
 """The BFV entry points at the C boundary (CPU tier: nothing is launched): include/hehub_amd.h declares the six calls -- the
 relinearising pair as a plain call and its _at twin with key_L0 after L --, hehub_amd/capi.py carries them with the header's argument
-counts and types, the library exports them, each refuses a NULL context, and the Engine has a method for each.  The refusals that need
+counts and types, and the Engine has a method for each (exported, typed as the header types them, refusing a NULL context: every
+call, tests/test_capi_symbols.py).  The refusals that need
 a context (every rule of the header comment, with its code, nothing enqueued): tests/test_gpu_bfv.py; what the calls compute: the same
 file; the arithmetic they are held to: tests/test_bfv_model.py; the host's base-size decision and constants: tests/test_bfv_host.py."""
 import inspect
-import os
-import re
 
-import pytest
+import abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PARAMS = {
     "hp_dev_bfv_lift": ["ctx", "logn", "L", "M", "moduli_qb", "polys", "d_in", "d_out"],
     "hp_dev_bfv_scale_round": ["ctx", "logn", "L", "M", "moduli_qb", "t", "polys", "d_in", "d_out"],
@@ -24,20 +22,8 @@ CALLS = tuple(PARAMS)
 METHODS = ("bfv_lift", "bfv_scale_round", "bfv_mult_low_level", "bfv_mult_hks", "bfv_decrypt_round")
 
 
-def header_parameters(names):
-    """{name: the parameter names} of the prototypes, comments stripped"""
-    text = open(os.path.join(ROOT, "include", "hehub_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    found = {}
-    for name in names:
-        m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, text)
-        assert m, name
-        found[name] = [re.findall(r"\w+", a)[-1] for a in m.group(1).split(",") if a.strip()]
-    return found
-
-
 def test_header_declares_the_six_calls():
-    assert header_parameters(CALLS) == PARAMS
+    assert {name: abi.parameter_names(name) for name in CALLS} == PARAMS
 
 
 def test_ctypes_table_matches_the_header():
@@ -51,24 +37,6 @@ def test_ctypes_table_matches_the_header():
             assert a is want, (name, p)
     plain, at = capi.SIGNATURES["hp_dev_bfv_mult_relin_hks"][1], capi.SIGNATURES["hp_dev_bfv_mult_relin_hks_at"][1]
     assert at == plain[:3] + [capi.szt] + plain[3:]   # (ctx, logn, L, key_L0, ...)
-
-
-def test_library_exports_the_calls():
-    import ctypes
-
-    from hehub_amd.build import build_lib
-
-    lib = ctypes.CDLL(build_lib())
-    assert not [n for n in CALLS if not hasattr(lib, n)]
-
-
-@pytest.mark.parametrize("name", CALLS)
-def test_null_context_is_refused(name):
-    from hehub_amd import capi
-
-    lib = capi.load()
-    _, args = capi.SIGNATURES[name]
-    assert getattr(lib, name)(*[None if a is capi.P else 0 for a in args]) == capi.HP_EINVAL
 
 
 def test_engine_has_a_method_for_every_call():

@@ -4,20 +4,22 @@ import ctypes
 import os
 import re
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import pytest
 
+import abi
+from hehub_amd import capi
 
-def header_functions():
-    text = open(os.path.join(ROOT, "include", "hehub_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(hp_[a-z0-9_]+)\s*\(", text)))
+ROOT = abi.ROOT
+# every entry point that returns a status and takes a context first (the hp_wire_ calls take a descriptor)
+TAKES_CONTEXT = [name for name, (res, args) in capi.SIGNATURES.items()
+                 if res is capi.INT and args and args[0] is capi.P and not name.startswith("hp_wire_")]
 
 
 def test_library_exports_every_declared_symbol():
     from hehub_amd.build import build_lib
 
     lib = ctypes.CDLL(build_lib())
-    names = header_functions()
+    names = sorted(abi.prototypes())
     assert len(names) >= 40
     missing = [n for n in names if not hasattr(lib, n)]
     assert not missing, missing
@@ -27,9 +29,15 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_ctypes_table_matches_header():
-    from hehub_amd import capi
-
-    assert sorted(capi.SIGNATURES) == header_functions()
+    """the same names, and for every one the restype and every argtypes entry of the header's type class (abi.CTYPES)"""
+    assert sorted(capi.SIGNATURES) == sorted(abi.prototypes())
+    for name, (ret, params) in abi.prototypes().items():
+        res, args = capi.SIGNATURES[name]
+        assert abi.agrees(res, ret), f"{name}: restype {res} for the header's `{ret}`"
+        assert len(args) == len(params), f"{name}: {len(args)} argtypes for the header's {[p for _, p in params]}"
+        for a, (cls, param) in zip(args, params):
+            assert abi.agrees(a, cls), f"{name}, parameter {param}: argtypes {a} for the header's `{cls}`"
+            assert param != "ctx" or a is capi.P, f"{name}: the context is passed as {a}"
     capi.load()
 
 
@@ -69,21 +77,15 @@ def test_public_header_is_plain_c(tmp_path):
     subprocess.run(["g++", "-std=c++11", "-Wall", "-Werror", f"-I{inc}", "-fsyntax-only", "-x", "c++", str(src)], check=True)
 
 
-def test_null_context_is_an_argument_error_everywhere():
+@pytest.mark.parametrize("name", TAKES_CONTEXT)
+def test_null_context_is_an_argument_error_everywhere(name):
     """every entry point that takes a context rejects NULL with HP_EINVAL before touching HIP: runs without a GPU"""
-    import ctypes as C
+    assert abi.null_context_call(capi.load(), name) == capi.HP_EINVAL
 
-    from hehub_amd import capi
 
+def test_null_context_special_cases():
     lib = capi.load()
-    checked = 0
-    for name, (res, args) in capi.SIGNATURES.items():
-        if res is not capi.INT or not args or args[0] is not capi.P or name.startswith("hp_wire_"):
-            continue
-        zeros = [None if a is capi.P or (isinstance(a, type) and issubclass(a, C._Pointer)) or a is C.c_char_p else 0 for a in args]
-        assert getattr(lib, name)(*zeros) == capi.HP_EINVAL, name
-        checked += 1
-    assert checked >= 60
+    assert len(TAKES_CONTEXT) >= 60
     assert lib.hp_ctx_create(0, None) == capi.HP_EINVAL
     assert lib.hp_last_error(None) == b"null context"
     assert lib.hp_ctx_workspace_bytes(None) == 0 and lib.hp_ctx_get_stream(None) is None

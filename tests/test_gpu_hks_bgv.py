@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import hks_bgv_model as B
+from gpu_words import at_both_levels, dev_i64, residues
 from hks_levels import embed_key, level_chain, level_digits, sub_key, top_chain
 from hks_model import chain, model_digits, residues_match
 from oracle.pyoracle import SplitMix
@@ -44,25 +45,8 @@ def eng():
     e.close()
 
 
-def at_both_levels(eng, run):
-    """{level: run()} at parity level B and at parity level A"""
-    got = {}
-    for level in ("B", "A"):
-        eng.set_parity_level(level)
-        try:
-            got[level] = run()
-            eng.sync()
-        finally:
-            eng.set_parity_level("B")
-    return got
-
-
 def nd_of(L, alpha):
     return (L + alpha - 1) // alpha
-
-
-def residues(x, q):
-    return x % np.array(q, dtype=U)[:, None]
 
 
 # ---- 1. the switch -----------------------------------------------------------------------------------------------------------------------
@@ -163,10 +147,6 @@ def test_relin_modswitch_and_mult_match_the_model(eng, orc, logn, L, k, alpha):
 
 
 # ---- 4. by decryption, with keys made on the device from error rows t * e -----------------------------------------------------------------
-def dev_i64(eng, x):
-    return eng.torch.from_numpy(np.ascontiguousarray(x, dtype=np.int64)).to(f"cuda:{eng.device}")
-
-
 def int64s(values):
     return np.array([int(v) for v in values], dtype=np.int64)
 

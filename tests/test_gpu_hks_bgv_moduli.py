@@ -30,6 +30,7 @@ import hks_bgv_model as B
 import hks_edges as H
 import moduli as M
 from dot_model import below_2q, model_dot, strict_rows
+from gpu_words import at_both_levels, case_id, dev_i64, residues
 from hks_levels import embed_key, level_chain, level_digits, sub_key
 from hks_model import model_digits, residues_match
 from oracle.pyoracle import SplitMix
@@ -39,10 +40,6 @@ pytestmark = pytest.mark.gpu
 U = np.uint64
 BATCH, T0 = E.BATCH, E.T0
 SPENT = {"model": 0.0, "start": None}
-
-
-def case_id(c):
-    return "-".join(str(x) for x in c)
 
 
 @pytest.fixture(scope="module")
@@ -65,23 +62,6 @@ class modelled:
 
     def __exit__(self, *exc):
         SPENT["model"] += time.perf_counter() - self.t0
-
-
-def at_both_levels(eng, run):
-    """{level: run()} at parity level B and in a level-A context (which keeps level B where the chain is not eligible)"""
-    got = {}
-    for level in ("B", "A"):
-        eng.set_parity_level(level)
-        try:
-            got[level] = run()
-            eng.sync()
-        finally:
-            eng.set_parity_level("B")
-    return got
-
-
-def residues(x, q):
-    return x % np.array(q, dtype=U)[:, None]
 
 
 def mismatch(got, exp, q):
@@ -393,10 +373,6 @@ def test_dot_of_the_largest_words_at_the_largest_term_count_of_one_launch(eng, o
 
 
 # ---- 6. by decryption, with keys made on the device from error rows t * e ---------------------------------------------------------------------
-def dev_i64(eng, x):
-    return eng.torch.from_numpy(np.ascontiguousarray(x, dtype=np.int64)).to(f"cuda:{eng.device}")
-
-
 @pytest.mark.parametrize("case", E.DECRYPT_CASES, ids=case_id)
 def test_mult_of_two_encryptions_decrypts_to_the_product(eng, orc, case):
     name, logn, L, k, alpha = case

@@ -12,6 +12,7 @@ import pytest
 
 import moduli as M
 import params as P
+from gpu_words import dev_i64
 from hks_model import centred, chain, decryption_errors, decryption_setup, keygen, rotations_of
 from oracle.pyoracle import SplitMix
 
@@ -54,10 +55,6 @@ class Draws:
         a, e = np.stack(self.a), np.stack(self.e)
         nd = len(self.a) // keys
         return eng.to_device(a.reshape((keys, nd) + a.shape[1:])), dev_i64(eng, e.reshape(keys, nd, -1))
-
-
-def dev_i64(eng, x):
-    return eng.torch.from_numpy(np.ascontiguousarray(x, dtype=np.int64)).to(f"cuda:{eng.device}")
 
 
 def ternary(rng, n):

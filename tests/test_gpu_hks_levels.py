@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import moduli as M
+from gpu_words import dev_i64
 from hks_levels import embed_diag, embed_key, level_chain, level_digits, level_rows, sub_key, top_chain
 from hks_model import centred_error, random_diagonal, rotations_of
 from oracle.pyoracle import SplitMix
@@ -192,10 +193,6 @@ def test_one_key_serves_a_chain_of_multiplications(eng):
 
 
 # ---- 6. the extracted key is the level's key -------------------------------------------------------------------------------------------
-def dev_i64(eng, x):
-    return eng.torch.from_numpy(np.ascontiguousarray(x, dtype=np.int64)).to(f"cuda:{eng.device}")
-
-
 @pytest.mark.parametrize("logn,key_L0,L,k,alpha", [SMALL, (4, 6, 2, 3, 3)])
 def test_the_extracted_key_is_the_level_key(eng, orc, logn, key_L0, L, k, alpha):
     """hp_dev_hks_keygen at the top and on the level's chain from the same secrets, the same e[d] and the level's rows of a: the

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import params as P
+from gpu_words import strict
 from oracle.pyoracle import SplitMix
 
 pytestmark = pytest.mark.gpu
@@ -77,12 +78,6 @@ def test_fork_shares_tables_and_keeps_own_workspace():
     finally:
         child.close()
         root.close()
-
-
-def strict(moduli, a):
-    """reduce_strict per limb (mod_arith.h:58-72): a [..., L, n] of lazy words below 2q"""
-    q = np.array(moduli, dtype=np.uint64)[:, None]
-    return np.where(a >= q, a - q, a)
 
 
 def test_family_members_driven_by_their_own_threads(orc):

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import params as P
+from gpu_words import strict
 from oracle.pyoracle import SplitMix
 from test_gpu_full_batch import PERIOD, all_equal_classes, tile
 from test_gpu_parity import _ntt_primes
@@ -26,12 +27,6 @@ def enga():
     yield e
     e.release_workspace()
     e.close()
-
-
-def strict(moduli, a):
-    """reduce_strict per limb: a [..., L, n] of lazy words below 2q"""
-    q = np.array(moduli, dtype=U)[:, None]
-    return np.where(a >= q, a - q, a)
 
 
 def canon(moduli, a):

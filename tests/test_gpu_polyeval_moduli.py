@@ -42,20 +42,17 @@ import hks_edges as H
 import moduli as M
 import polyeval_edges as PE
 from dot_model import below_2q, strict_rows
+from gpu_words import at_both_levels, case_id, dev_i64
 from hehub_amd.polyeval import Form, Plan
 from hks_levels import embed_key, level_chain, level_digits
 from oracle.pyoracle import SplitMix
 from polyeval_model import POWER7, decrypt_error, encrypt_constant, model_lincomb, model_plan
-from test_gpu_hks_bgv_moduli import at_both_levels, mismatch
+from test_gpu_hks_bgv_moduli import mismatch
 
 pytestmark = pytest.mark.gpu
 U = np.uint64
 BATCH, E0 = PE.BATCH, PE.E0
 SPENT = {"model": 0.0, "start": None}
-
-
-def case_id(c):
-    return "-".join(str(x) for x in c)
 
 
 @pytest.fixture(scope="module")
@@ -250,10 +247,6 @@ def test_whole_plans_under_a_key_for_one_more_modulus(eng, orc, name, logn):
 
 
 # ---- 5. by decryption ---------------------------------------------------------------------------------------------------------------------------
-def dev_i64(eng, x):
-    return eng.torch.from_numpy(np.ascontiguousarray(x, dtype=np.int64)).to(f"cuda:{eng.device}")
-
-
 @pytest.mark.parametrize("logn", PE.LOGNS)
 def test_power_plan_on_58_bit_limbs_decrypts_to_the_polynomial(eng, orc, logn):
     """WIDE58R (5, 1), alpha = 1, Delta = 2^58: the key made by hp_dev_hks_keygen from host-drawn uniform rows and errors, the

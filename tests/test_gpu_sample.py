@@ -11,6 +11,7 @@ import pytest
 
 import sample_cases as K
 import sample_model as S
+from gpu_words import dev_i64
 from hks_model import centred_error, chain, decryption_errors, keygen, rotations_of
 from oracle.pyoracle import SplitMix
 
@@ -26,10 +27,6 @@ def eng():
     e = Engine(0)
     yield e
     e.close()
-
-
-def dev_i64(eng, x):
-    return eng.torch.from_numpy(np.ascontiguousarray(x, dtype=np.int64)).to(f"cuda:{eng.device}")
 
 
 def signed_host(t):

@@ -1,14 +1,12 @@
 """The BGV hybrid entry points at the C boundary (CPU tier: nothing is launched): include/hehub_amd.h declares the four calls and their
 _at twins -- the plain call's parameters with key_L0 after L, plain_modulus directly after moduli_ext -- hehub_amd/capi.py carries them
-with the header's argument counts, the library exports them, each refuses a NULL context, and the Engine methods take key_L0 and out.
+as their CKKS twins with a 64-bit plain modulus, and the Engine methods take key_L0 and out (exported, typed as the header types them,
+refusing a NULL context: every call, tests/test_capi_symbols.py).
 What the calls compute: tests/test_gpu_hks_bgv.py; the arithmetic they are held to: tests/test_hks_bgv_model.py."""
 import inspect
-import os
-import re
 
-import pytest
+import abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PLAIN = ("hp_dev_bgv_hks_switch", "hp_dev_bgv_rotate_hoisted_hks", "hp_dev_bgv_relin_modswitch_hks",
          "hp_dev_bgv_mult_relin_modswitch_hks")
 CALLS = PLAIN + tuple(name + "_at" for name in PLAIN)
@@ -18,20 +16,8 @@ CKKS_TWIN = {"hp_dev_bgv_hks_switch": "hp_dev_hks_switch", "hp_dev_bgv_rotate_ho
 METHODS = ("bgv_hks_switch", "bgv_rotate_hoisted_hks", "bgv_relin_modswitch_hks", "bgv_mult_hks")
 
 
-def header_parameters(names):
-    """{name: the parameter names} of the prototypes, comments stripped"""
-    text = open(os.path.join(ROOT, "include", "hehub_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    found = {}
-    for name in names:
-        m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, text)
-        assert m, name
-        found[name] = [re.findall(r"\w+", a)[-1] for a in m.group(1).split(",") if a.strip()]
-    return found
-
-
 def test_header_declares_the_eight_calls():
-    params = header_parameters(CALLS + tuple(CKKS_TWIN.values()))
+    params = {name: abi.parameter_names(name) for name in CALLS + tuple(CKKS_TWIN.values())}
     for name in PLAIN:
         plain, at = params[name], params[name + "_at"]
         i = plain.index("L")
@@ -44,7 +30,7 @@ def test_header_declares_the_eight_calls():
 def test_ctypes_table_has_the_header_argument_counts():
     from hehub_amd import capi
 
-    params = header_parameters(CALLS)
+    params = {name: abi.parameter_names(name) for name in CALLS}
     for name in PLAIN:
         res, args = capi.SIGNATURES[name]
         res_at, args_at = capi.SIGNATURES[name + "_at"]
@@ -55,24 +41,6 @@ def test_ctypes_table_has_the_header_argument_counts():
         twin = capi.SIGNATURES[CKKS_TWIN[name]][1]
         i = params[name].index("plain_modulus")
         assert args[:i] + args[i + 1:] == twin, name
-
-
-def test_library_exports_the_calls():
-    import ctypes
-
-    from hehub_amd.build import build_lib
-
-    lib = ctypes.CDLL(build_lib())
-    assert not [n for n in CALLS if not hasattr(lib, n)]
-
-
-@pytest.mark.parametrize("name", CALLS)
-def test_null_context_is_refused(name):
-    from hehub_amd import capi
-
-    lib = capi.load()
-    _, args = capi.SIGNATURES[name]
-    assert getattr(lib, name)(*[None if a is capi.P else 0 for a in args]) == capi.HP_EINVAL
 
 
 def test_engine_methods_take_key_L0_and_out():

@@ -1,55 +1,14 @@
 """The key-generation entry points at the C boundary (CPU tier: nothing is launched): include/hehub_amd.h declares
-hp_dev_poly_from_signed, hp_dev_hks_keygen and hp_dev_hks_keygen_rot, hehub_amd/capi.py carries them with the header's argument
-counts, the library exports them, and each refuses a NULL context.  What they compute: tests/test_gpu_hks_keygen.py."""
-import os
-import re
+hp_dev_poly_from_signed, hp_dev_hks_keygen and hp_dev_hks_keygen_rot with these argument counts, and the Engine has the front-end
+methods (exported, typed as the header types them, refusing a NULL context: every call, tests/test_capi_symbols.py).  What they
+compute: tests/test_gpu_hks_keygen.py."""
+import abi
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CALLS = ("hp_dev_poly_from_signed", "hp_dev_hks_keygen", "hp_dev_hks_keygen_rot")
-
-
-def header_arguments():
-    """{name: number of parameters} of the three prototypes, comments stripped"""
-    text = open(os.path.join(ROOT, "include", "hehub_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    found = {}
-    for name in CALLS:
-        m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, text)
-        assert m, name
-        found[name] = len([a for a in m.group(1).split(",") if a.strip()])
-    return found
+COUNTS = {"hp_dev_poly_from_signed": 7, "hp_dev_hks_keygen": 12, "hp_dev_hks_keygen_rot": 13}
 
 
 def test_header_declares_the_calls():
-    assert header_arguments() == {"hp_dev_poly_from_signed": 7, "hp_dev_hks_keygen": 12, "hp_dev_hks_keygen_rot": 13}
-
-
-def test_ctypes_table_has_the_header_argument_counts():
-    from hehub_amd import capi
-
-    for name, count in header_arguments().items():
-        res, args = capi.SIGNATURES[name]
-        assert res is capi.INT and len(args) == count and args[0] is capi.P, name
-
-
-def test_library_exports_the_calls():
-    import ctypes
-
-    from hehub_amd.build import build_lib
-
-    lib = ctypes.CDLL(build_lib())
-    assert not [n for n in CALLS if not hasattr(lib, n)]
-
-
-@pytest.mark.parametrize("name", CALLS)
-def test_null_context_is_refused(name):
-    from hehub_amd import capi
-
-    lib = capi.load()
-    _, args = capi.SIGNATURES[name]
-    assert getattr(lib, name)(*[None if a is capi.P else 0 for a in args]) == capi.HP_EINVAL
+    assert {name: len(abi.parameter_names(name)) for name in COUNTS} == COUNTS
 
 
 def test_engine_has_the_front_end_methods():

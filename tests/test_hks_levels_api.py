@@ -1,19 +1,17 @@
 """The level-aware hybrid entry points at the C boundary (CPU tier: nothing is launched): include/hehub_amd.h declares an _at form of
-every hybrid call that takes a key -- the plain call's parameters with key_L0 after L -- hehub_amd/capi.py carries them with the
-header's argument counts, the library exports them, each refuses a NULL context, and the Engine methods take key_L0.  Then the claim
+every hybrid call that takes a key -- the plain call's parameters with key_L0 after L -- hehub_amd/capi.py carries them as the plain
+call's with a size_t after L, and the Engine methods take key_L0 (exported, typed as the header types them, refusing a NULL
+context: every call, tests/test_capi_symbols.py).  Then the claim
 the feature rests on, in plain integers: the digits of a level are contained in the top-level digits of the same index, and the row
 map of tests/hks_levels.py selects exactly the level's rows.  What the calls compute: tests/test_gpu_hks_levels.py."""
 import inspect
-import os
-import re
 
 import numpy as np
-import pytest
 
+import abi
 from hks_levels import level_chain, level_rows, sub_diag, sub_key, top_chain
 from hks_model import digits_of
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PLAIN = ("hp_dev_hks_switch", "hp_dev_ckks_rotate_hks", "hp_dev_ckks_conjugate_hks", "hp_dev_ckks_rotate_hoisted_hks",
          "hp_dev_ckks_lintrans_hks", "hp_dev_ckks_lintrans_bsgs_hks", "hp_dev_ckks_mult_relin_rescale_hks",
          "hp_dev_ckks_relin_rescale_hks", "hp_dev_ckks_dot_relin_rescale_hks")
@@ -22,22 +20,9 @@ METHODS = ("hks_switch", "ckks_rotate_hks", "ckks_conjugate_hks", "ckks_rotate_h
            "ckks_lintrans_bsgs_hks", "ckks_mult_hks", "ckks_relin_rescale_hks", "ckks_dot_hks")
 
 
-def header_parameters():
-    """{name: the parameter names} of the plain and the _at prototypes, comments stripped"""
-    text = open(os.path.join(ROOT, "include", "hehub_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    found = {}
-    for name in PLAIN + CALLS:
-        m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, text)
-        assert m, name
-        found[name] = [re.findall(r"\w+", a)[-1] for a in m.group(1).split(",") if a.strip()]
-    return found
-
-
 def test_header_declares_the_calls_with_key_L0_after_L():
-    params = header_parameters()
     for name in PLAIN:
-        plain, at = params[name], params[name + "_at"]
+        plain, at = abi.parameter_names(name), abi.parameter_names(name + "_at")
         assert len(at) == len(plain) + 1, name
         i = plain.index("L")
         assert at == plain[:i + 1] + ["key_L0"] + plain[i + 1:], name
@@ -46,30 +31,11 @@ def test_header_declares_the_calls_with_key_L0_after_L():
 def test_ctypes_table_has_the_header_argument_counts():
     from hehub_amd import capi
 
-    params = header_parameters()
     for name in PLAIN:
         res, args = capi.SIGNATURES[name + "_at"]
         plain_args = capi.SIGNATURES[name][1]
-        assert res is capi.INT and len(args) == len(params[name + "_at"]) == len(plain_args) + 1 and args[0] is capi.P, name
+        assert res is capi.INT and len(args) == len(abi.parameter_names(name + "_at")) == len(plain_args) + 1 and args[0] is capi.P, name
         assert args == plain_args[:3] + [capi.szt] + plain_args[3:], name   # (ctx, logn, L, key_L0, ...)
-
-
-def test_library_exports_the_calls():
-    import ctypes
-
-    from hehub_amd.build import build_lib
-
-    lib = ctypes.CDLL(build_lib())
-    assert not [n for n in CALLS if not hasattr(lib, n)]
-
-
-@pytest.mark.parametrize("name", CALLS)
-def test_null_context_is_refused(name):
-    from hehub_amd import capi
-
-    lib = capi.load()
-    _, args = capi.SIGNATURES[name]
-    assert getattr(lib, name)(*[None if a is capi.P else 0 for a in args]) == capi.HP_EINVAL
 
 
 def test_engine_methods_take_key_L0():

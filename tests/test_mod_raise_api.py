@@ -1,34 +1,21 @@
 """hp_dev_ckks_mod_raise at the C boundary (CPU tier: nothing is launched): include/hehub_amd.h declares it, hehub_amd/capi.py
-carries it with the header's argument count, the library exports it, it refuses a NULL context, the header states its refusals,
-its bound and what it leaves out, and the engine has the front-end method.  The refusals that need a context -- every HP_EINVAL and
-HP_EUNSUPPORTED of the header, each leaving d_out untouched -- and what the call computes: tests/test_gpu_mod_raise.py."""
-import ctypes as C
-import os
+carries it with these types, it refuses a NULL context whatever else it is given, the header states its refusals, its bound and
+what it leaves out, and the engine has the front-end method (exported, typed as the header types it: every call,
+tests/test_capi_symbols.py).  The refusals that need a context -- every HP_EINVAL and HP_EUNSUPPORTED of the header, each leaving
+d_out untouched -- and what the call computes: tests/test_gpu_mod_raise.py."""
 import re
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import abi
+
 CALL = "hp_dev_ckks_mod_raise"
 
 
-def header():
-    return open(os.path.join(ROOT, "include", "hehub_amd.h")).read()
-
-
-def prototype_arguments():
-    text = re.sub(r"/\*.*?\*/", "", header(), flags=re.S)
-    m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % CALL, text)
-    assert m
-    return [a.strip() for a in m.group(1).split(",") if a.strip()]
-
-
 def test_header_declares_the_call():
-    args = prototype_arguments()
-    assert len(args) == 8
-    assert [a.split()[-1].lstrip("*") for a in args] == ["ctx", "logn", "L", "moduli", "in_limbs", "batch", "d_ct", "d_out"]
+    assert abi.parameter_names(CALL) == ["ctx", "logn", "L", "moduli", "in_limbs", "batch", "d_ct", "d_out"]
 
 
 def test_header_states_refusals_and_bound():
-    m = re.search(r"/\* %s:(.*?)\*/" % CALL, header(), flags=re.S)
+    m = re.search(r"/\* %s:(.*?)\*/" % CALL, abi.header_text(), flags=re.S)
     assert m
     text = " ".join(m.group(1).replace("*", " ").split())
     for what in ("HP_EINVAL", "L < 2 or L > 32", "in_limbs == 0 or > 32", "batch == 0", "misaligned", "overlapping", "repeated modulus",
@@ -40,23 +27,14 @@ def test_header_states_refusals_and_bound():
 def test_ctypes_table_has_the_header_argument_count():
     from hehub_amd import capi
 
-    res, args = capi.SIGNATURES[CALL]
-    assert res is capi.INT and len(args) == len(prototype_arguments()) and args[0] is capi.P
-    assert args == [capi.P, capi.szt, capi.szt, capi.P, capi.szt, capi.szt, capi.P, capi.P]
-
-
-def test_library_exports_the_call():
-    from hehub_amd.build import build_lib
-
-    assert hasattr(C.CDLL(build_lib()), CALL)
+    assert capi.SIGNATURES[CALL] == (capi.INT, [capi.P, capi.szt, capi.szt, capi.P, capi.szt, capi.szt, capi.P, capi.P])
 
 
 def test_null_context_is_refused():
     from hehub_amd import capi
 
     lib = capi.load()
-    _, args = capi.SIGNATURES[CALL]
-    assert getattr(lib, CALL)(*[None if a is capi.P else 0 for a in args]) == capi.HP_EINVAL
+    assert abi.null_context_call(lib, CALL) == capi.HP_EINVAL
     buf = (capi.u64 * 4)(97, 193, 0, 0)
     assert getattr(lib, CALL)(None, 3, 2, buf, 1, 1, buf, buf) == capi.HP_EINVAL
 

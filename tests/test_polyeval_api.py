@@ -1,50 +1,26 @@
 """The polynomial-evaluation entry points at the C boundary (CPU tier: nothing is launched): include/hehub_amd.h declares
-hp_dev_ckks_lincomb and hp_dev_ckks_eval_plan_hks, hehub_amd/capi.py carries them with the header's argument counts and the plan's
-three structs field for field, the library exports them, each refuses a NULL context, and a plan of hehub_amd/polyeval.py marshals
-to those structs.  What they compute: tests/test_gpu_lincomb.py and tests/test_gpu_polyeval.py."""
+hp_dev_ckks_lincomb and hp_dev_ckks_eval_plan_hks with these argument counts, hehub_amd/capi.py carries the plan's three structs
+field for field, and a plan of hehub_amd/polyeval.py marshals to those structs (exported, typed as the header types them, refusing a
+NULL context: every call, tests/test_capi_symbols.py).  What they compute: tests/test_gpu_lincomb.py and tests/test_gpu_polyeval.py."""
 import ctypes as C
 import os
 import re
 
-import pytest
+import abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CALLS = ("hp_dev_ckks_lincomb", "hp_dev_ckks_eval_plan_hks")
-
-
-def header_text():
-    return re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "hehub_amd.h")).read(), flags=re.S)
-
-
-def header_arguments():
-    """{name: number of parameters} of the prototypes, comments stripped"""
-    text = header_text()
-    found = {}
-    for name in CALLS:
-        m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, text)
-        assert m, name
-        found[name] = len([a for a in m.group(1).split(",") if a.strip()])
-    return found
+ROOT = abi.ROOT
+COUNTS = {"hp_dev_ckks_lincomb": 11, "hp_dev_ckks_eval_plan_hks": 14}
 
 
 def test_header_declares_the_calls():
-    assert header_arguments() == {"hp_dev_ckks_lincomb": 11, "hp_dev_ckks_eval_plan_hks": 14}
+    assert {name: len(abi.parameter_names(name)) for name in COUNTS} == COUNTS
 
 
 def test_header_says_what_is_out_of_scope():
-    text = open(os.path.join(ROOT, "include", "hehub_amd.h")).read()
-    m = re.search(r"Out of scope:(.*?)\*/", text, flags=re.S)
+    m = re.search(r"Out of scope:(.*?)\*/", abi.header_text(), flags=re.S)
     assert m
     for what in ("tree-mode", "node", "sharded", "host layers", "encoding", "odd/even", "dead elements"):
         assert what in m.group(1), what
-
-
-def test_ctypes_table_has_the_header_argument_counts():
-    from hehub_amd import capi
-
-    for name, count in header_arguments().items():
-        res, args = capi.SIGNATURES[name]
-        assert res is capi.INT and len(args) == count and args[0] is capi.P, name
 
 
 def test_ctypes_structs_have_the_header_layout(tmp_path):
@@ -65,22 +41,6 @@ def test_ctypes_structs_have_the_header_layout(tmp_path):
     T, F, S = capi.EvalTerm, capi.EvalForm, capi.EvalStep
     assert got == [C.sizeof(T), T.coef.offset, C.sizeof(F), F.term.offset, F.cst.offset, C.sizeof(S), S.products.offset, S.x.offset,
                    S.y.offset, S.z.offset, T.elem.offset]
-
-
-def test_library_exports_the_calls():
-    from hehub_amd.build import build_lib
-
-    lib = C.CDLL(build_lib())
-    assert not [n for n in CALLS if not hasattr(lib, n)]
-
-
-@pytest.mark.parametrize("name", CALLS)
-def test_null_context_is_refused(name):
-    from hehub_amd import capi
-
-    lib = capi.load()
-    _, args = capi.SIGNATURES[name]
-    assert getattr(lib, name)(*[None if a is capi.P else 0 for a in args]) == capi.HP_EINVAL
 
 
 def test_engine_has_the_front_end_methods():

@@ -1,35 +1,22 @@
 """The sampling entry points at the C boundary (CPU tier: nothing is launched): include/hehub_amd.h declares the three samplers, the
-two seeded key generators and hp_dev_hks_key_expand, hehub_amd/capi.py carries them with the header's argument counts, the library
-exports them, and each refuses a NULL context.  What they compute: tests/test_gpu_sample.py."""
+two seeded key generators and hp_dev_hks_key_expand with these argument counts, and hehub_amd/capi.py passes the stream ids and the
+error scales as 64-bit values (exported, typed as the header types them, refusing a NULL context: every call,
+tests/test_capi_symbols.py).  What they compute: tests/test_gpu_sample.py."""
 import os
-import re
 
-import pytest
+import abi
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ROOT = abi.ROOT
 COUNTS = {"hp_dev_sample_uniform": 10, "hp_dev_sample_ternary": 6, "hp_dev_sample_cbd": 6, "hp_dev_hks_keygen_seeded": 13,
           "hp_dev_hks_keygen_rot_seeded": 14, "hp_dev_hks_key_expand": 10}
-CALLS = tuple(COUNTS)
-
-
-def header_arguments():
-    """{name: number of parameters} of the prototypes, comments stripped"""
-    text = open(os.path.join(ROOT, "include", "hehub_amd.h")).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    found = {}
-    for name in CALLS:
-        m = re.search(r"\bint\s+%s\s*\(([^)]*)\)\s*;" % name, text)
-        assert m, name
-        found[name] = len([a for a in m.group(1).split(",") if a.strip()])
-    return found
 
 
 def test_header_declares_the_calls():
-    assert header_arguments() == COUNTS
+    assert {name: len(abi.parameter_names(name)) for name in COUNTS} == COUNTS
 
 
 def test_header_carries_the_stream_table_and_what_is_out_of_scope():
-    text = open(os.path.join(ROOT, "include", "hehub_amd.h")).read()
+    text = abi.header_text()
     for phrase in ("attempt (bits 0-15) | kind << 16 (bits 16-23) | limb_id << 24 (bits 24-31)", "RFC 8439", "a wire kind for half keys",
                    "fixed-Hamming-weight", "discrete Gaussians", "sampling inside the inner", "node, sharded and C++ host layers"):
         assert phrase in text, phrase
@@ -38,32 +25,14 @@ def test_header_carries_the_stream_table_and_what_is_out_of_scope():
 def test_ctypes_table_has_the_header_argument_counts():
     from hehub_amd import capi
 
-    for name, count in header_arguments().items():
+    for name in COUNTS:
         res, args = capi.SIGNATURES[name]
-        assert res is capi.INT and len(args) == count and args[0] is capi.P, name
+        assert res is capi.INT and len(args) == len(abi.parameter_names(name)) and args[0] is capi.P, name
     # the stream id and the error scale are 64-bit values, not pointers
     assert capi.SIGNATURES["hp_dev_sample_uniform"][1][7] is capi.u64
     assert capi.SIGNATURES["hp_dev_hks_keygen_seeded"][1][10:12] == [capi.u64, capi.u64]
     assert capi.SIGNATURES["hp_dev_hks_keygen_rot_seeded"][1][11:13] == [capi.u64, capi.u64]
     assert capi.SIGNATURES["hp_dev_hks_key_expand"][1][8] is capi.u64
-
-
-def test_library_exports_the_calls():
-    import ctypes
-
-    from hehub_amd.build import build_lib
-
-    lib = ctypes.CDLL(build_lib())
-    assert not [n for n in CALLS if not hasattr(lib, n)]
-
-
-@pytest.mark.parametrize("name", CALLS)
-def test_null_context_is_refused(name):
-    from hehub_amd import capi
-
-    lib = capi.load()
-    _, args = capi.SIGNATURES[name]
-    assert getattr(lib, name)(*[None if a is capi.P else 0 for a in args]) == capi.HP_EINVAL
 
 
 def test_engine_has_the_front_end_methods():
